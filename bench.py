@@ -3,7 +3,22 @@
 reproj RMSE vs ref").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg5|cfg4|cfg3]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does what the headline figure needs and no more: it builds the
+problem, warms up, times the K steps, writes the outputs if asked to, and
+prints the result line (value, ms_per_step, the roofline and FP64 rates that
+follow from ms_per_step).  Everything under "Also reported" below takes runs
+of its own and is measured with --full only.
+
+--dump-outputs DIR: after the timed steps, what the timed solve left -- the
+arrays a caller of BAProblem.solve + download receives -- as float64 .npy
+files: cameras.npy (n_cams x 6: rotation vector, translation), points.npy
+(this rank's points x 3; points_rank<r>.npy on ranks r > 0) and cost.npy
+(initial cost, cost after the last timed step).  cfg5: 12 MB.  The problem is
+seeded, so two builds run with the same arguments can be compared array for
+array.
 
 Headline workload (value): BASELINE config 5, the config the 1/2/4/8 scaling
 curve is quoted on -- synthetic BA, 200 cameras / 500k points / 4M
@@ -15,7 +30,8 @@ sharded across ranks (strong scaling of the same problem), one RCCL
 all-reduce of the reduced camera system per iteration.  value = LM
 iterations / s of the job.
 
-Also reported: the same record for BASELINE config 4 (50 cams / 100k pts /
+Also reported (--full): the converged solve and the per-kernel split of the
+headline workload; the same record for BASELINE config 4 (50 cams / 100k pts /
 1M obs, the config of the north-star >= 50x target) under "cfg4"; RANSAC
 hypotheses/s on config 2 (5000 correspondences, 40 % outliers, 16384
 hypotheses); converged RMSE vs the reference's least-squares oracle; the
@@ -583,21 +599,37 @@ def ransac_leg(args, world, rank, local_rank, comm):
     return out, (x1, x2, samples)
 
 
-def ba_leg(workload, args, world, rank, local_rank, comm, barrier, allmax):
-    """One BA workload: the converged solve (RMSE), W warmup + K timed LM
-    iterations from x0 (barrier + synchronize around, max over ranks), and a
-    second run of the same K iterations with HIP events on for the per-phase
-    split (each event record costs the stream a few us, so the timed run has
-    none).  Every rank builds the same problem and keeps its point shard."""
+def dump_outputs(dirname, rank, cams, pts, rep):
+    """--dump-outputs: the timed solve's results as float64 .npy files (the
+    cameras are replicated: rank 0 writes them and the costs; every rank its
+    own point shard)."""
+    os.makedirs(dirname, exist_ok=True)
+    if rank == 0:
+        np.save(os.path.join(dirname, "cameras.npy"), np.asarray(cams, dtype=np.float64))
+        np.save(os.path.join(dirname, "cost.npy"), np.array([rep["cost0"], rep["cost"]], dtype=np.float64))
+    np.save(os.path.join(dirname, "points.npy" if rank == 0 else f"points_rank{rank}.npy"),
+            np.asarray(pts, dtype=np.float64))
+
+
+def ba_leg(workload, args, world, rank, local_rank, comm, barrier, allmax, dump=None):
+    """One BA workload: W warmup + K timed LM iterations from x0 (barrier +
+    synchronize around, max over ranks); `dump`: the directory the timed
+    solve's results are written to.  With --full also the converged solve
+    (RMSE) before them and, after them, a second run of the same K iterations
+    with HIP events on for the per-phase split (each event record costs the
+    stream a few us, so the timed run has none).  Every rank builds the same
+    problem and keeps its point shard."""
     prob = syn.ba_problem_cfg(workload, dense=False)
     cams0 = np.column_stack([prob["rotvec0"], np.einsum("nij,nj->ni", -prob["R0"], prob["C0"])])
     ci, pi, ob, X0, (lo, hi) = sfm_dist.shard_ba(prob["cam_idx"], prob["pt_idx"], prob["obs"], prob["X0"],
                                                  world, rank)
     ba = core.BAProblem(cams0, X0, ci, pi, ob, K, comm=comm, device=local_rank)
     ba.reset()
-    conv = ba.solve(max_iterations=100)
-    conv_c, conv_x = ba.download() if world > 1 else (None, None)
-    ba.reset()
+    conv = conv_c = conv_x = ktimes = None
+    if args.full:
+        conv = ba.solve(max_iterations=100)
+        conv_c, conv_x = ba.download() if world > 1 else (None, None)
+        ba.reset()
     ba.solve(max_iterations=args.warmup, fixed_iterations=True)
     ba.reset()
     barrier()
@@ -607,14 +639,17 @@ def ba_leg(workload, args, world, rank, local_rank, comm, barrier, allmax):
     torch.cuda.synchronize()
     barrier()
     dt = allmax(time.perf_counter() - t0)
-    ba.reset()
-    ba.set_timing(True)
-    ba.solve(max_iterations=args.steps, fixed_iterations=True)
-    ktimes = ba.kernel_times()
-    ba.set_timing(False)
+    if dump:
+        dump_outputs(dump, rank, *ba.download(), rep)
+    if args.full:
+        ba.reset()
+        ba.set_timing(True)
+        ba.solve(max_iterations=args.steps, fixed_iterations=True)
+        ktimes = ba.kernel_times()
+        ba.set_timing(False)
     ba.close()
     check = None
-    if world > 1:
+    if world > 1 and args.full:
         # multi-GPU correctness on the driver's node (after the timed region):
         # every rank must hold the same converged cost, and rank 0 re-solves
         # the whole problem alone on its GPU -- the sharded solve must take
@@ -646,8 +681,9 @@ def ba_leg(workload, args, world, rank, local_rank, comm, barrier, allmax):
 
 
 def ba_record(leg, args, world):
-    """The bench-line fields of one BA leg (value, roofline, fp64, per-kernel
-    split, step mix, RMSE)."""
+    """The bench-line fields of one BA leg: value, roofline, fp64, the timed
+    steps' mix, and with --full (the leg has a converged solve and a timed-
+    events run) the per-kernel split, the converged solve and the RMSE."""
     prob, workload = leg["prob"], leg["workload"]
     n_obs_total, n_pts_total = len(prob["cam_idx"]), prob["n_pts"]
     n_pairs = n_pairs_of(prob["pt_idx"][prob["pt_idx"] < leg["hi"]] if world > 1 else prob["pt_idx"])
@@ -659,7 +695,7 @@ def ba_record(leg, args, world):
     # measured time of an iteration (ms_per_step)
     iter_bytes = 52 * n_obs_total + 240 * n_pts_total
     ach = iter_bytes / (ms_per_step * 1e-3) / 1e9
-    pmc, pmc_src = pmc_iteration(workload) if world == 1 else ({}, None)
+    pmc, pmc_src = pmc_iteration(workload) if world == 1 and args.full else ({}, None)
     roof = {"kernel": "LM iteration (all kernels of one damped solve + trial evaluation)", "bound": "hbm",
             "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5),
             "traffic": int(sum(pmc.values())) if pmc else None, "algorithmic_bytes": int(iter_bytes),
@@ -669,7 +705,7 @@ def ba_record(leg, args, world):
             if pmc else None}
     flops = ba_flops(prob["pt_idx"], prob["n_cams"])
     kern = {}
-    for k, v in leg["ktimes"].items():
+    for k, v in (leg["ktimes"] or {}).items():
         e = {"ms": round(v, 4)}
         d = design_bytes(k, leg["n_obs_local"], leg["n_pts_local"], n_pairs, nblocks, ns)
         if d is not None:
@@ -681,7 +717,7 @@ def ba_record(leg, args, world):
             e["note"] = "reduced camera solve: persistent block Gauss-Jordan (one launch); flops = n^3/3 (Cholesky)"
         kern[k] = e
     conv, rep = leg["conv"], leg["rep"]
-    return {
+    rec = {
         "value": round(args.steps / leg["dt"], 3),
         "unit": "LM-iterations/s",
         "ms_per_step": round(ms_per_step, 4),
@@ -692,20 +728,25 @@ def ba_record(leg, args, world):
                  "peak_tflops": FP64_PEAK_TFLOPS,
                  "frac": round(flops / (ms_per_step * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 5),
                  "formula": "400 N_obs + sum_p(108 k_p + 216 k_p(k_p+1)/2) + (6 n_c)^3/3 (SURVEY §8(d))"},
-        "kernels_ms_per_iter": kern,
-        "pmc_bytes_per_iter": {k: int(v) for k, v in pmc.items()} if pmc else None,
         "step_mix": {"timed_steps": args.steps, "accepted": rep["accepted"],
                      "note": "fixed iterations from x0; the problem converges in ~5, later steps are rejected "
-                             "(a rejected step skips k_linearize / the camera blocks)",
-                     "converged_solve": {"iterations": conv["iterations"], "accepted": conv["accepted"],
-                                         "loop_ms": round(conv["t_loop_ms"], 3),
-                                         "ms_per_iteration": round(conv["t_loop_ms"] / max(1, conv["iterations"]), 4)}},
+                             "(a rejected step skips k_linearize / the camera blocks)"},
+    }
+    if not args.full:
+        return rec
+    rec["step_mix"]["converged_solve"] = {"iterations": conv["iterations"], "accepted": conv["accepted"],
+                                          "loop_ms": round(conv["t_loop_ms"], 3),
+                                          "ms_per_iteration": round(conv["t_loop_ms"] / max(1, conv["iterations"]), 4)}
+    rec.update({
+        "kernels_ms_per_iter": kern,
+        "pmc_bytes_per_iter": {k: int(v) for k, v in pmc.items()} if pmc else None,
         "converged_LM_it_per_s": round(conv["iterations"] / (conv["t_loop_ms"] * 1e-3), 2) if conv["t_loop_ms"] else None,
         **({"multi_rank_check": leg["check"]} if leg.get("check") else {}),
         "rmse": {f"{workload}_initial": round(syn.rmse_from_cost(conv["cost0"], n_obs_total), 6),
                  f"{workload}_gpu": round(syn.rmse_from_cost(conv["cost"], n_obs_total), 6),
                  "lm_iterations": conv["iterations"]},
-    }
+    })
+    return rec
 
 
 def main():
@@ -722,7 +763,15 @@ def main():
     ap.add_argument("--no-next-rows", action="store_true", help="skip the SURVEY §8(f) row measurements")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the dense perform_bundle_adjustment call")
     ap.add_argument("--no-shard-local", action="store_true", help="skip the per-rank shard bound")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the converged solve and the "
+                         "per-kernel split, the cfg4 sub-record, the drop-in end to end, the shard bound, RANSAC, "
+                         "the SURVEY §8(f) rows, the cfg3 RMSE and the CPU baselines (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's cameras, points and costs to DIR as float64 .npy files")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -752,22 +801,23 @@ def main():
             torch.distributed.broadcast_object_list(uid, src=0)
         comm = core.Comm(uid[0], world, rank, device=local_rank)
 
-    # ---------------- BA: the headline workload, then the cfg4 sub-record
-    legs = [ba_leg(args.workload, args, world, rank, local_rank, comm, barrier, allmax)]
-    second = None if args.no_secondary else ("cfg4" if args.workload != "cfg4" else None)
+    # ---------------- BA: the headline workload (a plain run stops here), then the cfg4 sub-record
+    legs = [ba_leg(args.workload, args, world, rank, local_rank, comm, barrier, allmax, dump=args.dump_outputs)]
+    second = None if args.no_secondary or not args.full else ("cfg4" if args.workload != "cfg4" else None)
     if second:
         legs.append(ba_leg(second, args, world, rank, local_rank, comm, barrier, allmax))
 
     # ---------------- the drop-in end to end, and the per-rank shard bound (N = 1 only)
     e2e, shards = {}, None
-    if world == 1 and not args.no_end_to_end:
+    if args.full and world == 1 and not args.no_end_to_end:
         for wl in [args.workload] + ([second] if second else []):
             e2e[wl] = end_to_end_ba(wl)
-    if world == 1 and not args.no_shard_local:
+    if args.full and world == 1 and not args.no_shard_local:
         shards = shard_local(args.workload, args.steps, args.warmup)
 
     # ---------------- RANSAC (config 2)
-    ransac, (x1, x2, samples) = ransac_leg(args, world, rank, local_rank, comm)
+    if args.full:
+        ransac, (x1, x2, samples) = ransac_leg(args, world, rank, local_rank, comm)
     if comm is not None:
         comm.close()
 
@@ -794,14 +844,21 @@ def main():
                    "parallelism": f"point-shard x{world} + RCCL all-reduce of the reduced camera system"},
         "roofline": head["roofline"],
         "fp64": head["fp64"],
+        "step_mix": head["step_mix"],
+    }
+    if not args.full:  # the plain run: the timed steps and what follows from them
+        print(json.dumps(out))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    out.update({
         "kernels_ms_per_iter": head["kernels_ms_per_iter"],
         "pmc_bytes_per_iter": head["pmc_bytes_per_iter"],
-        "step_mix": head["step_mix"],
         "converged_LM_it_per_s": head["converged_LM_it_per_s"],
         **({"multi_rank_check": head["multi_rank_check"]} if "multi_rank_check" in head else {}),
         "rmse": head["rmse"],
         "ransac": ransac,
-    }
+    })
     if second:
         out[second] = ba_record(legs[1], args, world)
     if args.workload in e2e:

@@ -142,7 +142,7 @@ def _rank_main(rank, world, port, q):
     torch.cuda.set_device = lambda d: None
     torch.cuda.synchronize = lambda *a, **k: None
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", str(STEPS), "--warmup", str(WARMUP), "--workload", "cfg3",
-                "--no-secondary", "--no-next-rows", "--ransac-hyps", str(HYPS)]
+                "--full", "--no-secondary", "--no-next-rows", "--ransac-hyps", str(HYPS)]
     out = io.StringIO()
     try:
         with contextlib.redirect_stdout(out):
@@ -184,3 +184,37 @@ def test_bench_two_rank_control_flow_gloo():
     mc = line["multi_rank_check"]
     assert res[0][3] == 1 and res[1][3] == 0 and mc["ranks"] == world and mc["cost_spread_over_ranks"] == 0.0
     assert mc["sharded"]["iterations"] == mc["single_rank"]["iterations"] and mc["ok"] is True
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(monkeypatch, tmp_path, capsys):
+    """A plain N = 1 run (no --full): the warmup and the timed solve are the
+    only solves, the line holds the headline fields and nothing that takes a
+    run of its own, and --dump-outputs writes what the timed solve left."""
+    import bench
+    import _sfmcore
+    fake = _FakeCore(_sfmcore)
+    monkeypatch.setattr(bench, "core", fake)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    dump = tmp_path / "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", str(STEPS), "--warmup", str(WARMUP),
+                                      "--workload", "cfg3", "--dump-outputs", str(dump)])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert fake.single_solves == 2 and fake.iter_allreduces == 0  # the warmup and the timed solve
+    assert line["metric"].startswith("BA LM-iterations/sec") and line["unit"] == "LM-iterations/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["n_gpus"] == 1
+    assert line["steps"] == STEPS and line["warmup"] == WARMUP and line["step_mix"]["timed_steps"] == STEPS
+    assert line["value"] > 0 and abs(line["ms_per_step"] - 1e3 / line["value"]) < 1e-3 * line["ms_per_step"] + 1e-3
+    for k in ("ransac", "cpu_baseline", "end_to_end", "shard_local", "next_rows", "cfg4", "rmse",
+              "kernels_ms_per_iter", "converged_LM_it_per_s"):
+        assert k not in line, k
+    assert sorted(os.listdir(dump)) == ["cameras.npy", "cost.npy", "points.npy"]
+    cams, pts, cost = (np.load(dump / f"{n}.npy") for n in ("cameras", "points", "cost"))
+    assert cams.dtype == pts.dtype == cost.dtype == np.float64
+    assert cams.shape == (6, 6) and pts.shape == (2000, 3) and cost.tolist() == [2.0e5, 1.0e5]
+    p = bench.syn.ba_problem(6, 2000, 5, seed=3, dense=False)  # the stand-in solve leaves x0: the seeded inputs
+    assert np.array_equal(pts, p["X0"]) and np.array_equal(cams[:, :3], p["rotvec0"])

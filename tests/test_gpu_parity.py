@@ -1183,14 +1183,47 @@ def test_bench_multi_rank_entry_runs_under_torchrun(tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", "--master-port=29517", os.path.join(repo, "bench.py"), "--gpus", "1",
-           "--steps", "3", "--warmup", "1", "--workload", "cfg3", "--no-cpu-baseline", "--ransac-hyps", "512",
-           "--force-comm"]
+           "--steps", "3", "--warmup", "1", "--workload", "cfg3", "--full", "--no-cpu-baseline",
+           "--ransac-hyps", "512", "--force-comm"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     import json
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 1 and d["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_timed_solve(core, tmp_path):
+    """A plain bench.py run with --dump-outputs (small workload): the line
+    holds the headline fields only, and the dumped cameras, points and costs
+    are those of the same fixed iterations from x0 solved here (the solve is
+    reproducible run to run, as test_ba_through_rccl_communicator asserts)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--workload", "cfg3", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["unit"] == "LM-iterations/s"
+    assert abs(d["ms_per_step"] - 1e3 / d["value"]) <= 1e-3 * d["ms_per_step"] + 1e-3
+    assert "ransac" not in d and "cpu_baseline" not in d and "cfg4" not in d and "kernels_ms_per_iter" not in d
+    p = syn.ba_problem_cfg("cfg3", dense=False)
+    cams0 = np.column_stack([p["rotvec0"], np.einsum("nij,nj->ni", -p["R0"], p["C0"])])
+    prob = core.BAProblem(cams0, p["X0"], p["cam_idx"], p["pt_idx"], p["obs"], K)
+    rep = prob.solve(max_iterations=3, fixed_iterations=True)
+    c1, x1 = prob.download()
+    prob.close()
+    assert rep["iterations"] == 3
+    assert sorted(os.listdir(dump)) == ["cameras.npy", "cost.npy", "points.npy"]
+    cams, pts, cost = (np.load(dump / f"{n}.npy") for n in ("cameras", "points", "cost"))
+    assert cams.dtype == pts.dtype == cost.dtype == np.float64
+    assert np.array_equal(cams, c1) and np.array_equal(pts, x1)
+    assert cost.tolist() == [rep["cost0"], rep["cost"]]
 
 
 @pytest.mark.parametrize("gtol", [1e9, 1e3, 1.0, 1e-2])

@@ -5,7 +5,7 @@
 # own time limit and the steps stop at the first failure; output goes under
 # gpurun_out/<out> (default: <what>).
 #   tests     the -m gpu suite, then smoke()
-#   bench     bench.py (N = 1, defaults)
+#   bench     bench.py --full (N = 1, defaults)
 #   solve     the reduced solve's per-pivot timeline (gjr_timeline.py, n = 1200
 #             and 300) and the BA kernel split with it and the Cholesky (gj_ab.py)
 #   e2e       the drop-in perform_bundle_adjustment at cfg4 and cfg5, with
@@ -21,7 +21,7 @@ tests)
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || exit 1
   tail -3 $OUT/gpu_tests.txt; tail -1 $OUT/smoke.txt ;;
 bench)
-  timeout -k 10 900 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+  timeout -k 10 900 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
   tail -c 600 $OUT/bench.json ;;
 solve)
   timeout -k 10 300 python -u tools/gj_ab.py SFM_SOLVE gj,chol 3 > $OUT/ab.txt 2>&1 || exit 1

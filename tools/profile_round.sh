@@ -8,9 +8,9 @@
 # failure, a counter pass that fails is recorded and skipped.
 OUT=gpurun_out/$1
 mkdir -p $OUT
-timeout -k 10 800 python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 800 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kernel_trace -o run --output-format csv -- python bench.py --no-cpu-baseline --no-next-rows > $OUT/prof.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kernel_trace -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-next-rows > $OUT/prof.log 2>&1 || exit 1
 timeout -s KILL 60 rocprofv3 --list-avail > $OUT/avail.txt 2>&1 || echo "list-avail failed" >> $OUT/passes.log
 for W in cfg4 cfg5; do
   timeout -k 10 120 rocprofv3 --kernel-trace --stats -d $OUT/$W/kernel_trace -o run --output-format csv -- python tools/ba_once.py $W 20 > $OUT/kt_$W.log 2>&1 || exit 1
