@@ -195,6 +195,28 @@ int sfm_triangulate_dlt(const double *P1, const double *P2, const double *x1, co
                         int64_t N, double *X, int device);
 
 /* ---------------------------------------------------------------------
+ * Two-view initialisation (ExtractCameraPose.py's candidates through
+ * LinearTriangulation.py and DisambiguateCameraPose.py:45-91).
+ * M pose candidates (1 <= M <= 8, else SFM_ERR_ARG) for camera 2: P2s
+ * (M x 3 x 4 projection matrices K[R | -RC], formed by the caller as for
+ * sfm_triangulate_dlt), Rs (M x 3 x 3), Cs (M x 3); camera 1: P1, R1, C1.
+ * A point counts for candidate m when it lies in front of both cameras:
+ * R1[2].(X - C1) > 0 and Rs[m][2].(X - Cs[m]) > 0.  *best: the first
+ * candidate with the strictly largest count (DisambiguateCameraPose.py:77).
+ * N == 0: every count 0, *best = 0.
+ * sfm_two_view_select: one launch triangulates x1, x2 (N x 2, uploaded once)
+ *   under every candidate and counts; X_best (N x 3) receives the winner's
+ *   points, X_all (M x N x 3, nullable) every candidate's.
+ * sfm_cheirality_count: the count alone on points already triangulated,
+ *   Xset (M x N x 3).
+ * ------------------------------------------------------------------- */
+int sfm_two_view_select(const double *P1, const double *P2s, const double *R1, const double *C1,
+                        const double *Rs, const double *Cs, int32_t M, const double *x1, const double *x2,
+                        int64_t N, int64_t *counts, int32_t *best, double *X_best, double *X_all, int device);
+int sfm_cheirality_count(const double *R1, const double *C1, const double *Rs, const double *Cs, int32_t M,
+                         const double *Xset, int64_t N, int64_t *counts, int32_t *best, int device);
+
+/* ---------------------------------------------------------------------
  * NonLinearTriangulation (NonLinearTriangulation.py:53-121): per point,
  * scipy least_squares(method='lm', max_nfev) of the 4-residual Loss
  * (:5-50) from X0[i]; MINPACK lmdif semantics (diag = ones, factor 100,

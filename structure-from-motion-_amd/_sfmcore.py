@@ -94,6 +94,8 @@ SIGNATURES = [
     ("sfm_matrix_to_rotvec", ctypes.c_int64, [_d, _i, _d]),
     ("sfm_rotvec_to_matrix", _c, [_d, _i, _d]),
     ("sfm_triangulate_dlt", _c, [_d, _d, _d, _d, _i, _d, _c]),
+    ("sfm_two_view_select", _c, [_d, _d, _d, _d, _d, _d, ctypes.c_int32, _d, _d, _i, _i64, _i32, _d, _d, _c]),
+    ("sfm_cheirality_count", _c, [_d, _d, _d, _d, ctypes.c_int32, _d, _i, _i64, _i32, _c]),
     ("sfm_triangulate_nonlinear", _c, [_d, _d, _d, _d, _d, _i, ctypes.c_int32, _d, _i32, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
@@ -641,6 +643,44 @@ def triangulate(P1, P2, x1, x2):
     X = np.zeros((len(x1), 3))
     _check(_lib.sfm_triangulate_dlt(_p(P1), _p(P2), _p(x1), _p(x2), len(x1), _p(X), DEVICE))
     return X
+
+
+def two_view_select(P1, P2s, R1, C1, Rs, Cs, x1, x2, return_all=False):
+    """Every pose candidate triangulated and its cheirality count taken in one
+    launch (sfm_two_view_select); P2s (M, 3, 4), Rs (M, 3, 3), Cs (M, 3).
+    Returns (counts (M,) int64, best, X_best (N, 3), X_all (M, N, 3) or None)."""
+    require_device()
+    P1, R1, C1 = _f64(P1, (3, 4)), _f64(R1, (3, 3)), _f64(C1, (3,))
+    M, N = len(P2s), len(x1)
+    if len(Rs) != M or len(Cs) != M or len(x2) != N:
+        raise ValueError("two_view_select: P2s, Rs, Cs need one entry per candidate and x1, x2 one row per point")
+    P2s, Rs, Cs = _f64(P2s, (M, 3, 4)), _f64(Rs, (M, 3, 3)), _f64(Cs, (M, 3))
+    x1, x2 = _f64(x1, (N, 2)), _f64(x2, (N, 2))
+    counts = np.zeros(M, dtype=np.int64)
+    best = np.zeros(1, dtype=np.int32)
+    X_best = np.zeros((N, 3))
+    X_all = np.zeros((M, N, 3)) if return_all else None
+    _check(_lib.sfm_two_view_select(_p(P1), _p(P2s), _p(R1), _p(C1), _p(Rs), _p(Cs), M, _p(x1), _p(x2), N,
+                                    _p(counts, _i64), _p(best, _i32), _p(X_best),
+                                    _p(X_all) if return_all else None, DEVICE))
+    return counts, int(best[0]), X_best, X_all
+
+
+def cheirality_count(R1, C1, Rs, Cs, Xset):
+    """Points in front of both cameras per candidate (sfm_cheirality_count);
+    Xset (M, N, 3).  Returns (counts (M,) int64, best)."""
+    require_device()
+    R1, C1 = _f64(R1, (3, 3)), _f64(C1, (3,))
+    Xset = _f64(Xset)
+    if Xset.ndim != 3 or Xset.shape[2] != 3 or len(Rs) != len(Xset) or len(Cs) != len(Xset):
+        raise ValueError("cheirality_count: Xset must be (M, N, 3) with one R and one C per candidate")
+    M, N = Xset.shape[:2]
+    Rs, Cs = _f64(Rs, (M, 3, 3)), _f64(Cs, (M, 3))
+    counts = np.zeros(M, dtype=np.int64)
+    best = np.zeros(1, dtype=np.int32)
+    _check(_lib.sfm_cheirality_count(_p(R1), _p(C1), _p(Rs), _p(Cs), M, _p(Xset), N, _p(counts, _i64),
+                                     _p(best, _i32), DEVICE))
+    return counts, int(best[0])
 
 
 def triangulate_nonlinear(P1, P2, x1, x2, X0, max_nfev=50):

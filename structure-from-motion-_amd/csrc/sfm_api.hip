@@ -11,6 +11,7 @@
 #include "sfm_geom.hpp"
 #include "dlt_general.hpp"
 #include "pyrandom.hpp"
+#include "triangulate_point.hpp"
 
 namespace sfm {
 
@@ -70,8 +71,7 @@ ThreadCtx *thread_ctx(int device) {
 
 // ---------------------------------------------------------------- kernels
 
-// LinearTriangulation.py:54-90: one thread per point, 4x4 DLT system,
-// right singular vector of the smallest singular value by one-sided Jacobi.
+// LinearTriangulation.py:54-90: one thread per point (triangulate_point).
 struct P2 {
     double p[24];
 };
@@ -81,24 +81,9 @@ __global__ void __launch_bounds__(256) k_triangulate(P2 P, const double2 *__rest
                                                      double *__restrict__ X) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const double *P1 = P.p, *Q = P.p + 12;
-    const double2 u = x1[i], v = x2[i];
-    double a[4][4], V[4][4];  // a[col][row]
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        a[c][0] = u.y * P1[8 + c] - P1[4 + c];
-        a[c][1] = P1[c] - u.x * P1[8 + c];
-        a[c][2] = v.y * Q[8 + c] - Q[4 + c];
-        a[c][3] = Q[c] - v.x * Q[8 + c];
-    }
-    jacobi_onesided<4, 4, 40>(a, V);
-    const int j = weakest_column<4, 4>(a);
-    const double h0 = V[0][j], h1 = V[1][j], h2 = V[2][j], h3 = V[3][j];
-    if (fabs(h3) > 1e-8) {
-        X[3 * i] = h0 / h3; X[3 * i + 1] = h1 / h3; X[3 * i + 2] = h2 / h3;
-    } else {
-        X[3 * i] = h0; X[3 * i + 1] = h1; X[3 * i + 2] = h2;
-    }
+    double Xi[3];
+    triangulate_point(P.p, P.p + 12, x1[i], x2[i], Xi);
+    X[3 * i] = Xi[0]; X[3 * i + 1] = Xi[1]; X[3 * i + 2] = Xi[2];
 }
 
 // project_points (BundleAdjustment.py:29-38)
