@@ -230,6 +230,44 @@ int sfm_triangulate_nonlinear(const double *P1, const double *P2, const double *
                               int device);
 
 /* ---------------------------------------------------------------------
+ * Multi-view track triangulation: one point per track from ALL of its views
+ * in one launch (the reference's registration loop, Wrapper_dev.py:262-291,
+ * triangulates image pairs one at a time and keeps the last pair's point).
+ * P: n_cams x 3 x 4 projection matrices K[R | -RC].  Tracks are CSR rows:
+ * track t owns observations [track_start[t], track_start[t+1]) of obs_cam
+ * (camera index) and obs_xy (n_obs x 2), cameras ascending within a track;
+ * track_start has T + 1 entries, starts at 0, never decreases and ends at
+ * n_obs, and every camera index lies in [0, n_cams) -- else SFM_ERR_ARG,
+ * checked on the host before anything is launched.  X0 (T x 3) is nullable
+ * except in SFM_TRACKS_REFINE mode.
+ * mode: SFM_TRACKS_LINEAR the N-view DLT (LinearTriangulation.py:54-90's
+ *   two rows per view, least singular vector, divided where |h3| > 1e-8);
+ *   SFM_TRACKS_REFINE Levenberg-Marquardt from X0 on the 2n residuals
+ *   u - h0/h2, v - h1/h2 (NonLinearTriangulation.py:5-50's loss over all
+ *   views; a view with |h2| < 1e-8 contributes none), ftol = xtol = gtol =
+ *   1e-8, at most max_nfev cost evaluations, only steps that lower the cost
+ *   accepted; SFM_TRACKS_BOTH the first, then the second from its result.
+ * A two-view track returns sfm_triangulate_dlt's and
+ * sfm_triangulate_nonlinear's bits.
+ * Outputs per track: X (T x 3); cost (T), the sum of squared residuals at X;
+ * front (T), 1 where X lies in front of every camera of the track (h2 > 0);
+ * info (T): >= 1 the refinement's stop code (1 ftol, 2 xtol, 3 both, 4 gtol,
+ * 5 max_nfev; MINPACK's info for a two-view track), 0 in SFM_TRACKS_LINEAR
+ * mode, -1 where the refinement's start has a NaN or residuals that are not
+ * finite (X is the start), -2 for a track of fewer than two views (X is
+ * X0's row where X0 is given and zeros otherwise, cost 0, front 0).
+ * The projections are staged in LDS up to SFM_TRACKS_LDS_CAMS cameras and
+ * read from global memory above; the results do not depend on which.
+ * T == 0 returns 0 without touching a device.
+ * ------------------------------------------------------------------- */
+#define SFM_TRACKS_LDS_CAMS 64
+enum { SFM_TRACKS_LINEAR = 0, SFM_TRACKS_REFINE = 1, SFM_TRACKS_BOTH = 2 };
+int sfm_triangulate_tracks(const double *P, int32_t n_cams, const int64_t *track_start, int64_t T,
+                           const int32_t *obs_cam, const double *obs_xy, int64_t n_obs, const double *X0,
+                           int32_t mode, int32_t max_nfev, double *X, double *cost, uint8_t *front,
+                           int32_t *info, int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

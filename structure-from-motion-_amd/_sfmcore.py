@@ -97,6 +97,8 @@ SIGNATURES = [
     ("sfm_two_view_select", _c, [_d, _d, _d, _d, _d, _d, ctypes.c_int32, _d, _d, _i, _i64, _i32, _d, _d, _c]),
     ("sfm_cheirality_count", _c, [_d, _d, _d, _d, ctypes.c_int32, _d, _i, _i64, _i32, _c]),
     ("sfm_triangulate_nonlinear", _c, [_d, _d, _d, _d, _d, _i, ctypes.c_int32, _d, _i32, _c]),
+    ("sfm_triangulate_tracks", _c, [_d, ctypes.c_int32, _i64, _i, _i32, _d, _i, _d, ctypes.c_int32, ctypes.c_int32,
+                                    _d, _d, _u8, _i32, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -694,6 +696,55 @@ def triangulate_nonlinear(P1, P2, x1, x2, X0, max_nfev=50):
     _check(_lib.sfm_triangulate_nonlinear(_p(P1), _p(P2), _p(x1), _p(x2), _p(X0), len(x1), int(max_nfev), _p(X),
                                           _p(info, _i32), DEVICE))
     return X, info
+
+
+TRACKS_LINEAR, TRACKS_REFINE, TRACKS_BOTH = 0, 1, 2  # sfmcore.h SFM_TRACKS_*
+
+
+def triangulate_tracks(P, track_start, obs_cam, obs_xy, X0=None, refine=True, max_nfev=50):
+    """One point per track from all of its views in one launch
+    (sfm_triangulate_tracks).  P (n_cams, 3, 4); the tracks are CSR rows:
+    track t owns obs_cam / obs_xy[track_start[t]:track_start[t + 1]], cameras
+    ascending.  refine=False: the N-view DLT.  refine=True: the DLT, then
+    Levenberg-Marquardt on all 2n residuals -- or, with X0 (T, 3), the
+    refinement alone from X0.  refine="only" is the latter and an error
+    without X0.  Returns (X (T, 3), cost (T,) sum of squared residuals at X,
+    front (T,) bool: X in front of every camera of the track, info (T,) int32:
+    >= 1 stop code, 0 not refined, -1 start kept, -2 fewer than two views).
+    The arguments are checked before a device is looked for, and T = 0
+    returns empty arrays without one."""
+    P = _f64(P).reshape(-1, 12)
+    ts = np.ascontiguousarray(track_start, dtype=np.int64).reshape(-1)
+    cam = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+    xy = _f64(obs_xy).reshape(-1, 2)
+    if len(ts) < 1 or len(xy) != len(cam):
+        raise ValueError("triangulate_tracks: track_start needs T + 1 entries and obs_cam, obs_xy one row per "
+                         "observation")
+    T = len(ts) - 1
+    if X0 is not None:
+        X0 = _f64(X0).reshape(-1, 3)
+        if len(X0) != T:
+            raise ValueError("triangulate_tracks: X0 must be (T, 3)")
+    if refine is False:
+        mode = TRACKS_LINEAR
+    elif refine is True:
+        mode = TRACKS_BOTH if X0 is None else TRACKS_REFINE
+    elif refine == "only":
+        mode = TRACKS_REFINE
+    else:
+        raise ValueError('triangulate_tracks: refine is True, False or "only"')
+    # the library checks the arguments itself and reports what is wrong with
+    # them; only a call that would reach the device asks for one first
+    bad = (int(max_nfev) <= 0 or ts[0] != 0 or np.any(np.diff(ts) < 0) or ts[-1] != len(cam) or (mode == TRACKS_REFINE and X0 is None)
+           or (len(cam) and (cam.min() < 0 or cam.max() >= len(P))))
+    if T and not bad:
+        require_device()
+    X, cost = np.zeros((T, 3)), np.zeros(T)
+    front, info = np.zeros(T, dtype=np.uint8), np.zeros(T, dtype=np.int32)
+    _check(_lib.sfm_triangulate_tracks(_p(P), len(P), _p(ts, _i64), T, _p(cam, _i32), _p(xy), len(cam),
+                                       _p(X0) if X0 is not None else None, mode, int(max_nfev), _p(X), _p(cost),
+                                       _p(front, _u8), _p(info, _i32), DEVICE))
+    return X, cost, front.astype(bool), info
 
 
 def reduced_solve(S, rhs):

@@ -57,6 +57,33 @@ class MatchStore:
         idx = self.lookup(rows, image)
         self.flag[idx[idx >= 0]] = value
 
+    def tracks(self, images, use_flags=True, min_views=2):
+        """CSR tracks over ``images`` (distinct, ascending image numbers): the
+        features with at least ``min_views`` observations among them (flagged
+        ones with ``use_flags``), each with all of those observations.
+        Returns (feature_rows, track_start, obs_cam, obs_xy): feature_rows
+        ascending, track t owning obs_cam / obs_xy[track_start[t]:
+        track_start[t + 1]], obs_cam the observation's position in ``images``
+        (ascending within a track) -- what np.where on the dense flags'
+        columns ``images`` gives, built from the COO rows alone."""
+        images = np.asarray(images, dtype=np.int64).reshape(-1)
+        if len(images) and (np.any(np.diff(images) <= 0) or images[0] < 0 or images[-1] >= self.n_images):
+            raise ValueError("tracks: images must be distinct, ascending and in [0, n_images)")
+        pos = np.full(self.n_images, -1, dtype=np.int32)
+        pos[images] = np.arange(len(images), dtype=np.int32)
+        keep = pos[self.image] >= 0
+        if use_flags:
+            keep &= self.flag == 1
+        # kept observations per feature row, from the rows' extents
+        before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+        per_row = before[self._row_start[1:]] - before[self._row_start[:-1]]
+        feature_rows = np.where(per_row >= max(int(min_views), 1))[0]
+        keep &= (per_row >= max(int(min_views), 1))[self.feature]
+        track_start = np.concatenate([[0], np.cumsum(per_row[feature_rows], dtype=np.int64)])
+        obs_cam = pos[self.image[keep]]
+        obs_xy = np.column_stack([self.x[keep], self.y[keep]])
+        return feature_rows, track_start, obs_cam, obs_xy
+
     def observations(self, filtered_world_coords, n_cameras, use_flags=True):
         """COO inputs of bundle adjustment in the reference's order
         (BundleAdjustment.py:164-169): valid points ascending, cameras
