@@ -268,6 +268,51 @@ int sfm_triangulate_tracks(const double *P, int32_t n_cams, const int64_t *track
                            int32_t *info, int device);
 
 /* ---------------------------------------------------------------------
+ * Robust multi-view track triangulation: sfm_triangulate_tracks trusts every
+ * observation; this finds, per track, the observations that agree on one
+ * point, fits the point to those alone and reports which they are.  The
+ * reference has no counterpart.  P, the CSR tracks and their checks are
+ * sfm_triangulate_tracks's; centres (n_cams x 3, nullable) are the camera
+ * centres, used for `angle` only.
+ * Hypotheses of a track of n >= 2 views are view pairs (i, j), i < j,
+ * positions inside the track, enumerated by decreasing index gap g = n-1 ..
+ * 1 and for each gap i = 0 .. n-1-g, the first max_pairs of them.  A pair's
+ * point is sfm_triangulate_dlt's for its two observations; one that is not
+ * finite counts 0.  An observation (u, v) is an inlier of a point with
+ * projection h where h2 > 0, not |h2| < 1e-8 and (u - h0/h2)^2 +
+ * (v - h1/h2)^2 < threshold^2.  The winner has the most inliers, then the
+ * smallest sum of its inliers' squared errors (added in observation order),
+ * then the earliest place in the enumeration.
+ * The winner's inliers are refitted as sfm_triangulate_tracks
+ * (SFM_TRACKS_BOTH) fits a track of those observations alone, bit for bit:
+ * three or more by the N-view DLT and Levenberg-Marquardt, exactly two by the
+ * two-view bodies.  The mask is then recomputed once against the refitted X.
+ * Outputs per track: X (T x 3); cost (T), the sum of the final inliers'
+ * squared errors; n_inliers (T); best_pair (T), the winner's place in the
+ * enumeration or -1; best_count (T), its inlier count; info (T): >= 1 the
+ * refinement's stop code and -1 as in sfm_triangulate_tracks, -2 fewer than
+ * two views (X zeros, nothing an inlier), -3 no hypothesis with min_inliers
+ * inliers (X is the best hypothesis's unrefined point; the mask, n_inliers
+ * and cost are that hypothesis's own); angle (T, nullable, and null where
+ * centres is null), the largest angle in radians between the rays X - C_i,
+ * X - C_j over pairs of final inliers (0 with fewer than two).  Nothing is
+ * gated on angle.  Per observation: inlier (n_obs), 1 or 0.
+ * threshold is in pixels, finite and > 0; max_pairs >= 1; min_inliers >= 2;
+ * max_nfev > 0.  lanes_per_track: the lanes of a wave that share one track's
+ * hypotheses, a power of two up to 64, or 0 to choose from the tracks'
+ * lengths and number; the results do not depend on it, nor on whether the
+ * projections are staged in LDS (n_cams <= SFM_TRACKS_LDS_CAMS).
+ * Every argument is checked on the host before anything is launched; T == 0
+ * returns 0 without touching a device.
+ * ------------------------------------------------------------------- */
+int sfm_triangulate_tracks_robust(const double *P, int32_t n_cams, const double *centres,
+                                  const int64_t *track_start, int64_t T, const int32_t *obs_cam,
+                                  const double *obs_xy, int64_t n_obs, double threshold, int32_t max_pairs,
+                                  int32_t min_inliers, int32_t max_nfev, int32_t lanes_per_track, double *X,
+                                  double *cost, int32_t *n_inliers, uint8_t *inlier, int32_t *best_pair,
+                                  int32_t *best_count, int32_t *info, double *angle, int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

@@ -99,6 +99,9 @@ SIGNATURES = [
     ("sfm_triangulate_nonlinear", _c, [_d, _d, _d, _d, _d, _i, ctypes.c_int32, _d, _i32, _c]),
     ("sfm_triangulate_tracks", _c, [_d, ctypes.c_int32, _i64, _i, _i32, _d, _i, _d, ctypes.c_int32, ctypes.c_int32,
                                     _d, _d, _u8, _i32, _c]),
+    ("sfm_triangulate_tracks_robust", _c, [_d, ctypes.c_int32, _d, _i64, _i, _i32, _d, _i, ctypes.c_double,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _d, _d,
+                                           _i32, _u8, _i32, _i32, _i32, _d, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -745,6 +748,63 @@ def triangulate_tracks(P, track_start, obs_cam, obs_xy, X0=None, refine=True, ma
                                        _p(X0) if X0 is not None else None, mode, int(max_nfev), _p(X), _p(cost),
                                        _p(front, _u8), _p(info, _i32), DEVICE))
     return X, cost, front.astype(bool), info
+
+
+def triangulate_tracks_robust(P, track_start, obs_cam, obs_xy, threshold=4.0, max_pairs=120, min_inliers=2,
+                              max_nfev=50, centres=None, lanes_per_track=0):
+    """Robust triangulate_tracks (sfm_triangulate_tracks_robust): per track,
+    view-pair hypotheses (widest index gap first, at most max_pairs) scored by
+    their inliers within ``threshold`` pixels, the winner's inliers refitted
+    as triangulate_tracks fits them alone, and the mask recomputed against the
+    refitted point.  P, track_start, obs_cam, obs_xy as triangulate_tracks;
+    centres (n_cams, 3) are the camera centres, needed for ``angle`` only.
+    Returns (X (T, 3), cost (T,) sum of the final inliers' squared errors,
+    n_inliers (T,) int32, inlier (n_obs,) bool, best_pair (T,) int32 the
+    winner's place in the enumeration or -1, best_count (T,) int32, info (T,)
+    int32: >= 1 stop code, -1 start kept, -2 fewer than two views, -3 no
+    hypothesis with min_inliers, angle (T,) the largest angle in radians
+    between the final inliers' rays, or None without centres).
+    lanes_per_track forces the kernel's lanes per track (0: chosen from the
+    tracks); the results do not depend on it.  The arguments are checked
+    before a device is looked for, and T = 0 returns empty arrays without one."""
+    P = _f64(P).reshape(-1, 12)
+    ts = np.ascontiguousarray(track_start, dtype=np.int64).reshape(-1)
+    cam = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+    xy = _f64(obs_xy).reshape(-1, 2)
+    if len(ts) < 1 or len(xy) != len(cam):
+        raise ValueError("triangulate_tracks_robust: track_start needs T + 1 entries and obs_cam, obs_xy one row "
+                         "per observation")
+    T = len(ts) - 1
+    if centres is not None:
+        centres = _f64(centres).reshape(-1, 3)
+        if len(centres) != len(P):
+            raise ValueError("triangulate_tracks_robust: centres must be (n_cams, 3)")
+    threshold, lanes = float(threshold), int(lanes_per_track)
+    # the library checks the arguments itself and reports what is wrong with
+    # them; only a call that would reach the device asks for one first
+    bad = (not (np.isfinite(threshold) and threshold > 0) or int(max_pairs) < 1 or int(min_inliers) < 2
+           or int(max_nfev) <= 0 or lanes < 0 or lanes > 64 or lanes & (lanes - 1) or ts[0] != 0
+           or np.any(np.diff(ts) < 0) or ts[-1] != len(cam) or (len(cam) and (cam.min() < 0 or cam.max() >= len(P))))
+    if T and not bad:
+        require_device()
+    X, cost = np.zeros((T, 3)), np.zeros(T)
+    n_inl, pair, count, info = (np.zeros(T, dtype=np.int32) for _ in range(4))
+    inlier = np.zeros(len(cam), dtype=np.uint8)
+    angle = np.zeros(T) if centres is not None else None
+    _check(_lib.sfm_triangulate_tracks_robust(
+        _p(P), len(P), _p(centres) if centres is not None else None, _p(ts, _i64), T, _p(cam, _i32), _p(xy), len(cam),
+        threshold, int(max_pairs), int(min_inliers), int(max_nfev), lanes, _p(X), _p(cost), _p(n_inl, _i32),
+        _p(inlier, _u8), _p(pair, _i32), _p(count, _i32), _p(info, _i32), _p(angle) if angle is not None else None,
+        DEVICE))
+    return X, cost, n_inl, inlier.astype(bool), pair, count, info, angle
+
+
+def track_pairs(n, max_pairs=120):
+    """The hypotheses of a track of n views in the kernel's order: pairs
+    (i, j), i < j, by decreasing index gap and for each gap i ascending, the
+    first max_pairs of them; (m, 2) int64."""
+    out = [(i, i + g) for g in range(n - 1, 0, -1) for i in range(n - g)]
+    return np.array(out[:max_pairs], dtype=np.int64).reshape(-1, 2)
 
 
 def reduced_solve(S, rhs):

@@ -57,7 +57,7 @@ class MatchStore:
         idx = self.lookup(rows, image)
         self.flag[idx[idx >= 0]] = value
 
-    def tracks(self, images, use_flags=True, min_views=2):
+    def tracks(self, images, use_flags=True, min_views=2, return_index=False):
         """CSR tracks over ``images`` (distinct, ascending image numbers): the
         features with at least ``min_views`` observations among them (flagged
         ones with ``use_flags``), each with all of those observations.
@@ -65,7 +65,10 @@ class MatchStore:
         ascending, track t owning obs_cam / obs_xy[track_start[t]:
         track_start[t + 1]], obs_cam the observation's position in ``images``
         (ascending within a track) -- what np.where on the dense flags'
-        columns ``images`` gives, built from the COO rows alone."""
+        columns ``images`` gives, built from the COO rows alone.  With
+        ``return_index`` a fifth array follows: the store index of every kept
+        observation (into feature / image / x / y / flag), in the tracks'
+        order, so that a per-observation result can be written back."""
         images = np.asarray(images, dtype=np.int64).reshape(-1)
         if len(images) and (np.any(np.diff(images) <= 0) or images[0] < 0 or images[-1] >= self.n_images):
             raise ValueError("tracks: images must be distinct, ascending and in [0, n_images)")
@@ -82,6 +85,8 @@ class MatchStore:
         track_start = np.concatenate([[0], np.cumsum(per_row[feature_rows], dtype=np.int64)])
         obs_cam = pos[self.image[keep]]
         obs_xy = np.column_stack([self.x[keep], self.y[keep]])
+        if return_index:
+            return feature_rows, track_start, obs_cam, obs_xy, np.where(keep)[0]
         return feature_rows, track_start, obs_cam, obs_xy
 
     def observations(self, filtered_world_coords, n_cameras, use_flags=True):

@@ -7,6 +7,12 @@ points over the last, so a feature seen in five images keeps the point of
 two of them.  ``triangulate_store`` differs on purpose: every flagged
 observation of a track enters the N-view DLT and the refinement
 (``sfm_triangulate_tracks``), with one upload of the observations.
+
+``triangulate_store_robust`` is the step between that and bundle adjustment:
+tracks built from pairwise matches hold wrong observations, and the bundle
+adjuster has no robust loss.  It fits every track to the observations that
+agree (``sfm_triangulate_tracks_robust``), says which tracks to keep and can
+clear the store's flags of everything else.
 """
 import numpy as np
 
@@ -28,3 +34,44 @@ def triangulate_store(store, K, C_set, R_set, images=None, refine=True):
     feature_rows, track_start, obs_cam, obs_xy = store.tracks(images)
     X, cost, front, info = _core.triangulate_tracks(P, track_start, obs_cam, obs_xy, refine=refine)
     return feature_rows, X, cost, front, info
+
+
+def triangulate_store_robust(store, K, C_set, R_set, images=None, threshold=4.0, min_inliers=3, min_angle_deg=0.0,
+                             update_flags=False):
+    """Robust ``triangulate_store``: the tracks of ``store`` over ``images``,
+    each fitted to its inlier observations (within ``threshold`` pixels).
+    Returns (feature_rows, out, keep): ``out`` is
+    ``_sfmcore.triangulate_tracks_robust``'s tuple (X, cost, n_inliers,
+    inlier, best_pair, best_count, info, angle), angle from C_set; ``keep``
+    (T,) bool marks the tracks with info >= 1, n_inliers >= min_inliers and
+    angle >= min_angle_deg.  With ``update_flags`` the store's flag is set to
+    0 for every outlier observation of a kept track and for every observation
+    of a dropped one, so that ``MatchStore.observations`` -- and the bundle
+    adjustment fed from it -- no longer sees them."""
+    images = np.arange(len(C_set)) if images is None else np.asarray(images)
+    if len(images) != len(C_set) or len(R_set) != len(C_set):
+        raise ValueError("triangulate_store_robust: one C and one R per image")
+    K = np.asarray(K, dtype=np.float64)
+    centres = np.array([np.asarray(C, dtype=np.float64).reshape(3) for C in C_set]).reshape(-1, 3)
+    P = np.stack([projection(K, C, np.asarray(R, dtype=np.float64)) for C, R in zip(centres, R_set)]) \
+        if len(C_set) else np.zeros((0, 3, 4))
+    feature_rows, track_start, obs_cam, obs_xy, index = store.tracks(images, return_index=True)
+    out = _core.triangulate_tracks_robust(P, track_start, obs_cam, obs_xy, threshold=threshold,
+                                          min_inliers=min_inliers, centres=centres)
+    keep = robust_keep(out, min_inliers, min_angle_deg)
+    if update_flags:
+        clear_outlier_flags(store, track_start, index, out[3], keep)
+    return feature_rows, out, keep
+
+
+def robust_keep(out, min_inliers, min_angle_deg):
+    """The tracks worth keeping among triangulate_tracks_robust's outputs"""
+    _, _, n_inliers, _, _, _, info, angle = out
+    return (info >= 1) & (n_inliers >= min_inliers) & (angle >= np.deg2rad(min_angle_deg))
+
+
+def clear_outlier_flags(store, track_start, index, inlier, keep):
+    """store.flag = 0 for the observations ``index`` (MatchStore.tracks'
+    return_index) that are outliers or belong to a track that is not kept"""
+    per_obs_keep = np.repeat(np.asarray(keep, dtype=bool), np.diff(track_start))
+    store.flag[index[~(np.asarray(inlier, dtype=bool) & per_obs_keep)]] = 0
