@@ -313,6 +313,59 @@ int sfm_triangulate_tracks_robust(const double *P, int32_t n_cams, const double 
                                   int32_t *best_count, int32_t *info, double *angle, int device);
 
 /* ---------------------------------------------------------------------
+ * Batched view registration: 6-point PnP RANSAC and a pose refit for every
+ * candidate view in one call (the reference registers one image per call from
+ * 4-point samples, Wrapper_dev.py:232-249; differs on purpose).
+ * K 3 x 3; X (n_pts x 3) the points.  The V views are CSR rows: view v owns
+ * correspondences [view_start[v], view_start[v+1]) of pt_idx (index into X) and
+ * xy (n_corr x 2); view_start has V + 1 entries, starts at 0, never decreases
+ * and ends at n_corr, every pt_idx lies in [0, n_pts).  samples (V x H x 6):
+ * each entry a position inside its view, in [0, n_v), the six of a hypothesis
+ * distinct; ignored for views of n_v < 6.  A violation is SFM_ERR_ARG, found on
+ * the host before anything is launched.
+ * Hypothesis: the 12 x 12 DLT system of the six sampled correspondences, its
+ * right singular vector of the smallest singular value (one-sided Jacobi),
+ * [M | t] with the sign that makes det M > 0, split as M = L R (L lower
+ * triangular, positive diagonal; det R = 1), scale = mean(diag L), C = -R^T t /
+ * scale.  The hypothesis is scored under its own projection P = K [M | t] /
+ * scale, the 11-parameter fit of its six points (`models`); (C, R) is the pose
+ * the refit starts from.  One whose model is not finite scores 0.  An observation (u, v) is an inlier of P where, with
+ * h = P [X; 1], h2 > 0, not |h2| < 1e-8 and (u - h0/h2)^2 + (v - h1/h2)^2 <
+ * threshold^2 (the fp64 expression decides).  The winner has the most inliers,
+ * then the earliest place in the table.
+ * Refit: Levenberg-Marquardt on six pose parameters (rotation increment
+ * multiplied from the left, C additive) over the current inliers, lambda 1e-3,
+ * / 10 on an accepted and x 10 on a rejected step, only steps that lower the
+ * cost accepted, MINPACK's stop tests at 1e-8 and at most max_nfev cost
+ * evaluations; every correspondence of the view is then scored against the
+ * refitted pose, and (count, then smaller cost) replaces the current state only
+ * if it is not worse; up to refit_rounds rounds, ending early when the mask does
+ * not change.  So n_inliers >= best_count.
+ * Outputs per view: C (V x 3), R (V x 9), cost (sum of the final inliers'
+ * squared errors), n_inliers, best_hyp (-1 without one), best_count, info:
+ * 1..5 the last refit's stop code (1 ftol, 2 xtol, 3 both, 4 gtol, 5 max_nfev),
+ * 0 refit_rounds = 0, -1 n_v < 6 (C = 0, R = I, nothing an inlier; nothing of
+ * the view is read on or from the device), -2 no finite hypothesis (the same
+ * outputs), -3 best_count < min_inliers (the winning hypothesis's pose, mask,
+ * count and cost, no refit), -4 the refit's start had no finite cost (as -3).
+ * Per correspondence: inlier (n_corr), 1 or 0.  Nullable: counts (V x H) the
+ * inliers per hypothesis, models (V x H x 12) the hypothesis projections; both
+ * zero for a view of n_v < 6.
+ * threshold is in pixels, finite and > 0; H >= 1; min_inliers >= 6;
+ * refit_rounds >= 0; max_nfev > 0.  No sum depends on the batch: a view's
+ * outputs are the same bits alone, in any batch and at any place in it.
+ * Two launches and one synchronisation whatever V is; V == 0, or no view of six
+ * correspondences, returns without touching a device.  sfm_last_timings: upload,
+ * both kernels, download, the fit-and-score kernel alone.
+ * ------------------------------------------------------------------- */
+int sfm_register_views(const double *K, const double *X, int64_t n_pts, const int64_t *view_start, int64_t V,
+                       const int32_t *pt_idx, const double *xy, int64_t n_corr, const int32_t *samples,
+                       int64_t H, double threshold, int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev,
+                       double *C, double *R, double *cost, int32_t *n_inliers, int32_t *best_hyp,
+                       int32_t *best_count, int32_t *info, uint8_t *inlier, int32_t *counts, double *models,
+                       int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

@@ -102,6 +102,9 @@ SIGNATURES = [
     ("sfm_triangulate_tracks_robust", _c, [_d, ctypes.c_int32, _d, _i64, _i, _i32, _d, _i, ctypes.c_double,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _d, _d,
                                            _i32, _u8, _i32, _i32, _i32, _d, _c]),
+    ("sfm_register_views", _c, [_d, _d, _i, _i64, _i, _i32, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32,
+                                ctypes.c_int32, ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32, _d,
+                                _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -805,6 +808,97 @@ def track_pairs(n, max_pairs=120):
     first max_pairs of them; (m, 2) int64."""
     out = [(i, i + g) for g in range(n - 1, 0, -1) for i in range(n - g)]
     return np.array(out[:max_pairs], dtype=np.int64).reshape(-1, 2)
+
+
+def register_samples(counts, H, seed):
+    """The 6-point sample table of register_views for views of ``counts``
+    correspondences: (V, H, 6) int32, each entry a position inside its view,
+    the six of a hypothesis distinct.  View v draws from child v of
+    numpy.random.default_rng(seed) -- integers(0, n_v, (H, 6)), the rows that
+    hold a duplicate redrawn until none do -- so its table does not depend on
+    the other views; a view of n_v < 6 gets zeros."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    H = int(H)
+    if H < 1:
+        raise ValueError("register_samples: H must be at least 1")
+    out = np.zeros((len(counts), H, 6), dtype=np.int32)
+    root = np.random.SeedSequence(seed)
+    for v, n in enumerate(counts):
+        if n < 6:
+            continue
+        # child v of the seed, whatever the number of views
+        rng = np.random.default_rng(np.random.SeedSequence(root.entropy, spawn_key=(v,)))
+        t = rng.integers(0, n, (H, 6))
+        while True:
+            s = np.sort(t, axis=1)
+            dup = np.where((s[:, 1:] == s[:, :-1]).any(axis=1))[0]
+            if not len(dup):
+                break
+            t[dup] = rng.integers(0, n, (len(dup), 6))
+        out[v] = t
+    return out
+
+
+def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,
+                   want_counts=False, want_models=False):
+    """Batched view registration (sfm_register_views): for every view, 6-point
+    PnP RANSAC over the host-drawn ``samples`` (V, H, 6; register_samples), the
+    winner's pose refitted to its consensus set by Levenberg-Marquardt in up
+    to ``refit_rounds`` rounds, and the inlier mask of the view's
+    correspondences.  X (n_pts, 3); the views are CSR rows: view v owns
+    pt_idx / xy[view_start[v]:view_start[v + 1]], pt_idx an index into X.
+    Returns (C (V, 3), R (V, 3, 3), cost (V,) sum of the final inliers' squared
+    errors, n_inliers (V,) int32, inlier (n_corr,) bool, best_hyp (V,) int32,
+    best_count (V,) int32, info (V,) int32: 1..5 the last refit's stop code, 0
+    no refit asked for, -1 fewer than six correspondences, -2 no finite
+    hypothesis, -3 best_count < min_inliers, -4 refit could not start), then
+    counts (V, H) int32 with want_counts and models (V, H, 3, 4) with
+    want_models.  The arguments are checked before a device is looked for;
+    V = 0, or no view of six correspondences, returns without one."""
+    K = _f64(K).reshape(3, 3)
+    X = _f64(X).reshape(-1, 3)
+    vs = np.ascontiguousarray(view_start, dtype=np.int64).reshape(-1)
+    pt = np.ascontiguousarray(pt_idx, dtype=np.int32).reshape(-1)
+    xy = _f64(xy).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    if len(vs) < 1 or len(xy) != len(pt):
+        raise ValueError("register_views: view_start needs V + 1 entries and pt_idx, xy one row per correspondence")
+    V = len(vs) - 1
+    if samples.ndim != 3 or samples.shape[0] != V or samples.shape[2] != 6 or samples.shape[1] < 1:
+        raise ValueError("register_views: samples must be (V, H, 6) with H >= 1")
+    H = samples.shape[1]
+    threshold = float(threshold)
+    # the library checks the arguments itself and reports what is wrong with
+    # them; only a call that would reach the device asks for one first
+    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 6 or int(refit_rounds) < 0
+           or int(max_nfev) <= 0 or vs[0] != 0 or np.any(np.diff(vs) < 0) or vs[-1] != len(pt)
+           or (len(pt) and (pt.min() < 0 or pt.max() >= len(X))))
+    if not bad:
+        n_v = np.diff(vs)
+        live = n_v >= 6
+        if live.any():
+            s = samples[live]
+            srt = np.sort(s, axis=2)
+            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_v[live]).any()
+                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
+            if not bad:
+                require_device()
+    C, R, cost = np.zeros((V, 3)), np.zeros((V, 9)), np.zeros(V)
+    n_inl, hyp, count, info = (np.zeros(V, dtype=np.int32) for _ in range(4))
+    inlier = np.zeros(len(pt), dtype=np.uint8)
+    counts = np.zeros((V, H), dtype=np.int32) if want_counts else None
+    models = np.zeros((V, H, 12)) if want_models else None
+    _check(_lib.sfm_register_views(
+        _p(K), _p(X), len(X), _p(vs, _i64), V, _p(pt, _i32), _p(xy), len(pt), _p(samples, _i32), H, threshold,
+        int(min_inliers), int(refit_rounds), int(max_nfev), _p(C), _p(R), _p(cost), _p(n_inl, _i32), _p(hyp, _i32),
+        _p(count, _i32), _p(info, _i32), _p(inlier, _u8), _p(counts, _i32) if want_counts else None,
+        _p(models) if want_models else None, DEVICE))
+    out = (C, R.reshape(V, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info)
+    if want_counts:
+        out += (counts,)
+    if want_models:
+        out += (models.reshape(V, H, 3, 4),)
+    return out
 
 
 def reduced_solve(S, rhs):

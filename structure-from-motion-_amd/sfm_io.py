@@ -89,6 +89,39 @@ class MatchStore:
             return feature_rows, track_start, obs_cam, obs_xy, np.where(keep)[0]
         return feature_rows, track_start, obs_cam, obs_xy
 
+    def correspondences(self, feature_rows, images, use_flags=True):
+        """2D-3D correspondences of candidate views: for each image of
+        ``images`` (distinct image numbers, any order) its observations whose
+        feature is one of ``feature_rows`` (distinct rows: the features that
+        have a point) and, with ``use_flags``, whose flag is 1 -- what
+        np.where(filtered_world_coords[:, 0] & filtered_feature_flags[:, img])
+        selects on the dense matrices (Wrapper_dev.py:232-239), built from the
+        COO arrays alone.  Returns view-major CSR (view_start, pt_idx, xy,
+        index): view v = images[v] owns [view_start[v], view_start[v + 1]),
+        features ascending within it; pt_idx is the feature's position in
+        ``feature_rows``, xy the observation, index its place in the store."""
+        rows = np.asarray(feature_rows, dtype=np.int64).reshape(-1)
+        images = np.asarray(images, dtype=np.int64).reshape(-1)
+        if len(images) and (images.min() < 0 or images.max() >= self.n_images
+                            or len(np.unique(images)) != len(images)):
+            raise ValueError("correspondences: images must be distinct and in [0, n_images)")
+        if len(rows) and (rows.min() < 0 or rows.max() >= self.n_features or len(np.unique(rows)) != len(rows)):
+            raise ValueError("correspondences: feature_rows must be distinct and in [0, n_features)")
+        pos_row = np.full(self.n_features, -1, dtype=np.int64)
+        pos_row[rows] = np.arange(len(rows))
+        pos_img = np.full(self.n_images, -1, dtype=np.int64)
+        pos_img[images] = np.arange(len(images))
+        keep = (pos_row[self.feature] >= 0) & (pos_img[self.image] >= 0)
+        if use_flags:
+            keep &= self.flag == 1
+        index = np.where(keep)[0]
+        view = pos_img[self.image[index]]
+        index = index[np.argsort(view, kind="stable")]  # the store is feature-major: features stay ascending
+        view_start = np.concatenate([[0], np.cumsum(np.bincount(view, minlength=len(images)), dtype=np.int64)])
+        pt_idx = pos_row[self.feature[index]].astype(np.int32)
+        xy = np.column_stack([self.x[index], self.y[index]])
+        return view_start.astype(np.int64), pt_idx, xy, index
+
     def observations(self, filtered_world_coords, n_cameras, use_flags=True):
         """COO inputs of bundle adjustment in the reference's order
         (BundleAdjustment.py:164-169): valid points ascending, cameras

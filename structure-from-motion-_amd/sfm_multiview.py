@@ -64,6 +64,30 @@ def triangulate_store_robust(store, K, C_set, R_set, images=None, threshold=4.0,
     return feature_rows, out, keep
 
 
+def register_views(store, K, feature_rows, X, candidates, H=256, seed=0, threshold=4.0, min_inliers=6,
+                   update_flags=False):
+    """Which image to register next, and with what pose: every image of
+    ``candidates`` against the points X (row i belongs to feature_rows[i]) in
+    one device call (``_sfmcore.register_views``: 6-point PnP RANSAC over H
+    hypotheses per view, pose refit, inlier mask).  It replaces the
+    reference's per-image PnPRANSAC + NonlinearPnP (Wrapper_dev.py:232-249).
+    Returns (order, out, index): ``out`` is ``_sfmcore.register_views``'s tuple
+    (C, R, cost, n_inliers, inlier, best_hyp, best_count, info) over the CSR
+    correspondences of ``store.correspondences(feature_rows, candidates)``,
+    ``index`` their store indices, ``order`` the candidates by decreasing
+    n_inliers (stable), so candidates[order[0]] is the next best view.  With
+    ``update_flags`` the store's flag is set to 0 for the outlier
+    observations of every view with info >= 1."""
+    view_start, pt_idx, xy, index = store.correspondences(feature_rows, candidates)
+    samples = _core.register_samples(np.diff(view_start), H, seed)
+    out = _core.register_views(K, X, view_start, pt_idx, xy, samples, threshold=threshold, min_inliers=min_inliers)
+    order = np.argsort(-out[3].astype(np.int64), kind="stable")
+    if update_flags:
+        registered = np.repeat(out[7] >= 1, np.diff(view_start))
+        store.flag[index[registered & ~out[4]]] = 0
+    return order, out, index
+
+
 def robust_keep(out, min_inliers, min_angle_deg):
     """The tracks worth keeping among triangulate_tracks_robust's outputs"""
     _, _, n_inliers, _, _, _, info, angle = out
