@@ -707,6 +707,13 @@ def triangulate_nonlinear(P1, P2, x1, x2, X0, max_nfev=50):
 TRACKS_LINEAR, TRACKS_REFINE, TRACKS_BOTH = 0, 1, 2  # sfmcore.h SFM_TRACKS_*
 
 
+def _csr_ok(start, idx, n_targets):
+    """The library's CSR checks.  It makes them itself and reports what is
+    wrong; only a call that would reach the device asks for one first."""
+    return bool(start[0] == 0 and not np.any(np.diff(start) < 0) and start[-1] == len(idx)
+                and (not len(idx) or (idx.min() >= 0 and idx.max() < n_targets)))
+
+
 def triangulate_tracks(P, track_start, obs_cam, obs_xy, X0=None, refine=True, max_nfev=50):
     """One point per track from all of its views in one launch
     (sfm_triangulate_tracks).  P (n_cams, 3, 4); the tracks are CSR rows:
@@ -739,10 +746,7 @@ def triangulate_tracks(P, track_start, obs_cam, obs_xy, X0=None, refine=True, ma
         mode = TRACKS_REFINE
     else:
         raise ValueError('triangulate_tracks: refine is True, False or "only"')
-    # the library checks the arguments itself and reports what is wrong with
-    # them; only a call that would reach the device asks for one first
-    bad = (int(max_nfev) <= 0 or ts[0] != 0 or np.any(np.diff(ts) < 0) or ts[-1] != len(cam) or (mode == TRACKS_REFINE and X0 is None)
-           or (len(cam) and (cam.min() < 0 or cam.max() >= len(P))))
+    bad = int(max_nfev) <= 0 or (mode == TRACKS_REFINE and X0 is None) or not _csr_ok(ts, cam, len(P))
     if T and not bad:
         require_device()
     X, cost = np.zeros((T, 3)), np.zeros(T)
@@ -783,11 +787,8 @@ def triangulate_tracks_robust(P, track_start, obs_cam, obs_xy, threshold=4.0, ma
         if len(centres) != len(P):
             raise ValueError("triangulate_tracks_robust: centres must be (n_cams, 3)")
     threshold, lanes = float(threshold), int(lanes_per_track)
-    # the library checks the arguments itself and reports what is wrong with
-    # them; only a call that would reach the device asks for one first
     bad = (not (np.isfinite(threshold) and threshold > 0) or int(max_pairs) < 1 or int(min_inliers) < 2
-           or int(max_nfev) <= 0 or lanes < 0 or lanes > 64 or lanes & (lanes - 1) or ts[0] != 0
-           or np.any(np.diff(ts) < 0) or ts[-1] != len(cam) or (len(cam) and (cam.min() < 0 or cam.max() >= len(P))))
+           or int(max_nfev) <= 0 or lanes < 0 or lanes > 64 or lanes & (lanes - 1) or not _csr_ok(ts, cam, len(P)))
     if T and not bad:
         require_device()
     X, cost = np.zeros((T, 3)), np.zeros(T)
@@ -868,11 +869,8 @@ def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inl
         raise ValueError("register_views: samples must be (V, H, 6) with H >= 1")
     H = samples.shape[1]
     threshold = float(threshold)
-    # the library checks the arguments itself and reports what is wrong with
-    # them; only a call that would reach the device asks for one first
     bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 6 or int(refit_rounds) < 0
-           or int(max_nfev) <= 0 or vs[0] != 0 or np.any(np.diff(vs) < 0) or vs[-1] != len(pt)
-           or (len(pt) and (pt.min() < 0 or pt.max() >= len(X))))
+           or int(max_nfev) <= 0 or not _csr_ok(vs, pt, len(X)))
     if not bad:
         n_v = np.diff(vs)
         live = n_v >= 6

@@ -2616,11 +2616,6 @@ struct SweepPlan {
     }
 };
 
-static int env_int(const char *name, int dflt) {
-    const char *v = std::getenv(name);
-    return v ? std::atoi(v) : dflt;
-}
-
 // k_backsub_trial's grid when the cameras fit its LDS stage: the resident
 // workgroup count for that LDS size (every workgroup starts at once), at most
 // the partial-sum slots; 0 selects the global-camera kernel

@@ -19,7 +19,7 @@
 // 8 * 20 B of observations and writes 37 B, against ~10^4 flops.
 #include <cstring>
 
-#include "sfm_common.hpp"
+#include "staging.hpp"
 // triangulate_point.hpp comes before lm_small.hpp on purpose: lm_small.hpp
 // turns FP contraction off for the rest of the translation unit, and the DLT
 // body must be compiled as sfm_api.hip and two_view.hip compile it to return
@@ -108,8 +108,6 @@ k_triangulate_tracks(const double *__restrict__ Pg, int32_t n_cams, const int64_
     info_out[t] = info;
 }
 
-static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace sfm
 
 using namespace sfm;
@@ -124,67 +122,41 @@ extern "C" int sfm_triangulate_tracks(const double *P, int32_t n_cams, const int
     SFM_CHECK_ARG(max_nfev > 0, "max_nfev must be positive");
     SFM_CHECK_ARG(mode != MV_REFINE || X0, "refine-only mode needs X0");
     SFM_CHECK_ARG(track_start, "null pointer");
-    SFM_CHECK_ARG(track_start[0] == 0, "track_start does not start at 0");
-    for (int64_t t = 0; t < T; ++t)
-        SFM_CHECK_ARG(track_start[t + 1] >= track_start[t], "track_start decreases");
-    SFM_CHECK_ARG(track_start[T] == n_obs, "track_start does not end at the observation count");
+    SFM_TRY(check_csr(track_start, T, n_obs, "track_start", "observation"));
     SFM_CHECK_ARG(n_obs == 0 || (obs_cam && obs_xy && P), "null pointer");
-    // a camera index out of range is an error here, never a device read
-    for (int64_t k = 0; k < n_obs; ++k)
-        SFM_CHECK_ARG(obs_cam[k] >= 0 && obs_cam[k] < n_cams, "camera index outside [0, n_cams)");
+    SFM_TRY(check_index(obs_cam, n_obs, n_cams, "camera index outside [0, n_cams)"));
     if (T == 0) return 0;
     SFM_CHECK_ARG(X && cost && front && info, "null pointer");
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    // buf[0]: track_start | obs_xy | obs_cam | X0 | P;  buf[1]: X | cost | info | front
-    const size_t b_ts = (size_t)(T + 1) * sizeof(int64_t), b_xy = (size_t)n_obs * sizeof(double2),
-                 b_cam = (size_t)n_obs * sizeof(int32_t), b_x = (size_t)T * 3 * sizeof(double),
-                 b_p = (size_t)n_cams * 12 * sizeof(double);
-    const size_t o_xy = up256(b_ts), o_cam = o_xy + up256(b_xy), o_x0 = o_cam + up256(b_cam),
-                 o_p = o_x0 + up256(b_x), in_bytes = o_p + up256(b_p);
-    const size_t o_cost = up256(b_x), o_info = o_cost + up256((size_t)T * sizeof(double)),
-                 o_front = o_info + up256((size_t)T * sizeof(int32_t)), out_bytes = o_front + up256((size_t)T);
-    int rc;
-    if ((rc = c->buf[0].reserve(in_bytes)) || (rc = c->buf[1].reserve(out_bytes))) return rc;
-    char *in = c->buf[0].as<char>(), *out = c->buf[1].as<char>();
+    Pack in(c->buf[0]), out(c->buf[1]);
+    const auto i_ts = in.add<int64_t>(T + 1);
+    const auto i_xy = in.add<double2>(n_obs);
+    const auto i_cam = in.add<int32_t>(n_obs);
+    const auto i_x0 = in.add<double>(3 * T), i_p = in.add<double>(12 * (size_t)n_cams);
+    const auto o_x = out.add<double>(3 * T), o_cost = out.add<double>(T);
+    const auto o_info = out.add<int32_t>(T);
+    const auto o_front = out.add<uint8_t>(T);
+    SFM_TRY(in.reserve());
+    SFM_TRY(out.reserve());
     hipStream_t s = c->stream;
-    const bool tm = call_timing();  // HIP events only when asked (each costs the stream us)
-    if (tm) SFM_HIP(hipEventRecord(c->ev[0], s));
-    SFM_HIP(hipMemcpyAsync(in, track_start, b_ts, hipMemcpyHostToDevice, s));
-    if (n_obs) {
-        SFM_HIP(hipMemcpyAsync(in + o_xy, obs_xy, b_xy, hipMemcpyHostToDevice, s));
-        SFM_HIP(hipMemcpyAsync(in + o_cam, obs_cam, b_cam, hipMemcpyHostToDevice, s));
-    }
-    if (X0) SFM_HIP(hipMemcpyAsync(in + o_x0, X0, b_x, hipMemcpyHostToDevice, s));
-    if (n_cams) SFM_HIP(hipMemcpyAsync(in + o_p, P, b_p, hipMemcpyHostToDevice, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[1], s));
-    const dim3 grid(ceil_div(T, 256)), block(256);
-    const double *dX0 = X0 ? reinterpret_cast<const double *>(in + o_x0) : nullptr;
-    if (n_cams <= MV_LDS_CAMS)
-        hipLaunchKernelGGL(k_triangulate_tracks<true>, grid, block, 0, s, reinterpret_cast<const double *>(in + o_p),
-                           n_cams, reinterpret_cast<const int64_t *>(in), reinterpret_cast<const int32_t *>(in + o_cam),
-                           reinterpret_cast<const double2 *>(in + o_xy), dX0, T, mode, max_nfev,
-                           reinterpret_cast<double *>(out), reinterpret_cast<double *>(out + o_cost),
-                           reinterpret_cast<uint8_t *>(out + o_front), reinterpret_cast<int32_t *>(out + o_info));
-    else
-        hipLaunchKernelGGL(k_triangulate_tracks<false>, grid, block, 0, s, reinterpret_cast<const double *>(in + o_p),
-                           n_cams, reinterpret_cast<const int64_t *>(in), reinterpret_cast<const int32_t *>(in + o_cam),
-                           reinterpret_cast<const double2 *>(in + o_xy), dX0, T, mode, max_nfev,
-                           reinterpret_cast<double *>(out), reinterpret_cast<double *>(out + o_cost),
-                           reinterpret_cast<uint8_t *>(out + o_front), reinterpret_cast<int32_t *>(out + o_info));
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(in.upload(i_ts, track_start, s));
+    SFM_TRY(in.upload(i_xy, obs_xy, s));
+    SFM_TRY(in.upload(i_cam, obs_cam, s));
+    SFM_TRY(in.upload(i_x0, X0, s));
+    SFM_TRY(in.upload(i_p, P, s));
+    SFM_TRY(tm.mark(s));
+    auto kernel = n_cams <= MV_LDS_CAMS ? k_triangulate_tracks<true> : k_triangulate_tracks<false>;
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(T, 256)), dim3(256), 0, s, in.ptr(i_p), n_cams, in.ptr(i_ts),
+                       in.ptr(i_cam), in.ptr(i_xy), X0 ? in.ptr(i_x0) : nullptr, T, mode, max_nfev, out.ptr(o_x),
+                       out.ptr(o_cost), out.ptr(o_front), out.ptr(o_info));
     SFM_HIP(hipGetLastError());
-    if (tm) SFM_HIP(hipEventRecord(c->ev[2], s));
-    SFM_HIP(hipMemcpyAsync(X, out, b_x, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(cost, out + o_cost, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(info, out + o_info, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(front, out + o_front, (size_t)T, hipMemcpyDeviceToHost, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[3], s));
-    SFM_HIP(hipStreamSynchronize(s));
-    float a = 0, b = 0, d = 0;
-    if (tm) (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-    if (tm) (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
-    if (tm) (void)hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
-    const double t4[4] = {a, b, d, b};
-    set_timings(t4, 4);
-    return 0;
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(out.download(X, o_x, s));
+    SFM_TRY(out.download(cost, o_cost, s));
+    SFM_TRY(out.download(info, o_info, s));
+    SFM_TRY(out.download(front, o_front, s));
+    return tm.finish(s);
 }

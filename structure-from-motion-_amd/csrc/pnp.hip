@@ -961,11 +961,6 @@ __global__ void __launch_bounds__(NL2_THREADS) k_nonlinear_pnp(const double *__r
 
 using namespace sfm;
 
-static int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
 static int load_cam(const double *K, Cam3 &c) {
     std::memcpy(c.k, K, sizeof c.k);
     return 0;

@@ -29,7 +29,7 @@
 #include <cstring>
 
 #include "lm_small.hpp"
-#include "sfm_common.hpp"
+#include "staging.hpp"
 #include "pnp_model.hpp"
 #include "select.hpp"
 #include "sfm_geom.hpp"
@@ -638,8 +638,6 @@ k_reg_refine(const double *__restrict__ Xg, const int64_t *__restrict__ view_sta
     }
 }
 
-static size_t rv_up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace sfm
 
 using namespace sfm;
@@ -658,19 +656,12 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
     SFM_CHECK_ARG(max_nfev > 0, "max_nfev must be positive");
     SFM_CHECK_ARG(V < (int64_t)0x7fffffff / H, "V x H too large for one call");
     SFM_CHECK_ARG(view_start && K, "null pointer");
-    SFM_CHECK_ARG(view_start[0] == 0, "view_start does not start at 0");
+    SFM_TRY(check_csr(view_start, V, n_corr, "view_start", "correspondence", 0x7fffffff,
+                      "a view has too many correspondences"));
     int64_t n_live = 0;
-    for (int64_t v = 0; v < V; ++v) {
-        const int64_t n = view_start[v + 1] - view_start[v];
-        SFM_CHECK_ARG(n >= 0, "view_start decreases");
-        SFM_CHECK_ARG(n <= (int64_t)0x7fffffff, "a view has too many correspondences");
-        if (n >= 6) ++n_live;
-    }
-    SFM_CHECK_ARG(view_start[V] == n_corr, "view_start does not end at the correspondence count");
+    for (int64_t v = 0; v < V; ++v) n_live += view_start[v + 1] - view_start[v] >= 6;
     SFM_CHECK_ARG(n_corr == 0 || (pt_idx && xy && X), "null pointer");
-    // an index out of range is an error here, never a device read
-    for (int64_t k = 0; k < n_corr; ++k)
-        SFM_CHECK_ARG(pt_idx[k] >= 0 && pt_idx[k] < n_pts, "point index outside [0, n_pts)");
+    SFM_TRY(check_index(pt_idx, n_corr, n_pts, "point index outside [0, n_pts)"));
     SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
     for (int64_t v = 0; v < V; ++v) {
         const int64_t n = view_start[v + 1] - view_start[v];
@@ -724,57 +715,45 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
     }
     blk[n_live] = (int32_t)blocks;
 
-    // buf[0]: view_start | xy | X | pt_idx | samples | block table
-    // buf[1]: C | R | cost | info | n_inliers | best_hyp | best_count | counts | modelsP | modelsCR | inlier | mask2
     const size_t VH = (size_t)V * (size_t)H;
-    const size_t b_vs = (size_t)(V + 1) * sizeof(int64_t), b_xy = (size_t)n_corr * sizeof(double2),
-                 b_X = (size_t)n_pts * 3 * sizeof(double), b_pt = (size_t)n_corr * sizeof(int32_t),
-                 b_s = VH * 6 * sizeof(int32_t), b_t = (size_t)(3 * n_live + 1) * sizeof(int32_t);
-    const size_t o_xy = rv_up256(b_vs), o_X = o_xy + rv_up256(b_xy), o_pt = o_X + rv_up256(b_X),
-                 o_s = o_pt + rv_up256(b_pt), o_t = o_s + rv_up256(b_s), in_bytes = o_t + rv_up256(b_t);
-    const size_t b_C = (size_t)V * 3 * sizeof(double), b_R = (size_t)V * 9 * sizeof(double),
-                 b_d = (size_t)V * sizeof(double), b_i = (size_t)V * sizeof(int32_t), b_cnt = VH * sizeof(int32_t),
-                 b_m = VH * 12 * sizeof(double);
-    const size_t o_R = rv_up256(b_C), o_cost = o_R + rv_up256(b_R), o_info = o_cost + rv_up256(b_d),
-                 o_ninl = o_info + rv_up256(b_i), o_hyp = o_ninl + rv_up256(b_i), o_bc = o_hyp + rv_up256(b_i),
-                 o_cnt = o_bc + rv_up256(b_i), o_mP = o_cnt + rv_up256(b_cnt), o_mCR = o_mP + rv_up256(b_m),
-                 o_mask = o_mCR + rv_up256(b_m), o_m2 = o_mask + rv_up256((size_t)n_corr),
-                 out_bytes = o_m2 + rv_up256((size_t)n_corr);
-    if ((rc = c->buf[0].reserve(in_bytes)) || (rc = c->buf[1].reserve(out_bytes))) return rc;
-    char *in = c->buf[0].as<char>(), *out = c->buf[1].as<char>();
+    Pack in(c->buf[0]), out(c->buf[1]);
+    const auto i_vs = in.add<int64_t>(V + 1);
+    const auto i_xy = in.add<double2>(n_corr);
+    const auto i_X = in.add<double>(3 * n_pts);
+    const auto i_pt = in.add<int32_t>(n_corr), i_s = in.add<int32_t>(6 * VH);
+    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto o_C = out.add<double>(3 * V), o_R = out.add<double>(9 * V), o_cost = out.add<double>(V);
+    const auto o_info = out.add<int32_t>(V), o_ninl = out.add<int32_t>(V);
+    const auto o_hyp = out.add<int32_t>(V), o_bc = out.add<int32_t>(V), o_cnt = out.add<int32_t>(VH);
+    const auto o_mP = out.add<double>(12 * VH), o_mCR = out.add<double>(12 * VH);
+    const auto o_mask = out.add<uint8_t>(n_corr), o_m2 = out.add<uint8_t>(n_corr);  // o_m2: the refits' trial mask
+    SFM_TRY(in.reserve());
+    SFM_TRY(out.reserve());
     Cam3 cam;
     std::memcpy(cam.k, K, sizeof cam.k);
     hipStream_t s = c->stream;
-    const bool tm = call_timing();  // HIP events only when asked (each costs the stream us)
-    if (tm) SFM_HIP(hipEventRecord(c->ev[0], s));
-    SFM_HIP(hipMemcpyAsync(in, view_start, b_vs, hipMemcpyHostToDevice, s));
-    SFM_HIP(hipMemcpyAsync(in + o_xy, xy, b_xy, hipMemcpyHostToDevice, s));
-    SFM_HIP(hipMemcpyAsync(in + o_X, X, b_X, hipMemcpyHostToDevice, s));
-    SFM_HIP(hipMemcpyAsync(in + o_pt, pt_idx, b_pt, hipMemcpyHostToDevice, s));
-    SFM_HIP(hipMemcpyAsync(in + o_s, samples, b_s, hipMemcpyHostToDevice, s));
-    SFM_HIP(hipMemcpyAsync(in + o_t, blk, b_t, hipMemcpyHostToDevice, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[1], s));
-    const double *dX = reinterpret_cast<const double *>(in + o_X);
-    const int64_t *dvs = reinterpret_cast<const int64_t *>(in);
-    const int32_t *dpt = reinterpret_cast<const int32_t *>(in + o_pt);
-    const double2 *dxy = reinterpret_cast<const double2 *>(in + o_xy);
-    const int32_t *dblk = reinterpret_cast<const int32_t *>(in + o_t);
-    double *dmP = reinterpret_cast<double *>(out + o_mP), *dmCR = reinterpret_cast<double *>(out + o_mCR);
-    int32_t *dcnt = reinterpret_cast<int32_t *>(out + o_cnt);
-    hipLaunchKernelGGL(k_reg_fit_score, dim3((unsigned)blocks), dim3(RV_THREADS), 0, s, dX, dvs, dpt, dxy,
-                       reinterpret_cast<const int32_t *>(in + o_s), (int32_t)H, cam, dblk, dblk + (n_live + 1),
-                       (int32_t)n_live, threshold, dmP, dmCR, dcnt);
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(in.upload(i_vs, view_start, s));
+    SFM_TRY(in.upload(i_xy, xy, s));
+    SFM_TRY(in.upload(i_X, X, s));
+    SFM_TRY(in.upload(i_pt, pt_idx, s));
+    SFM_TRY(in.upload(i_s, samples, s));
+    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(tm.mark(s));
+    hipLaunchKernelGGL(k_reg_fit_score, dim3((unsigned)blocks), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
+                       in.ptr(i_pt), in.ptr(i_xy), in.ptr(i_s), (int32_t)H, cam, in.ptr(i_t),
+                       in.ptr(i_t, n_live + 1), (int32_t)n_live, threshold, out.ptr(o_mP), out.ptr(o_mCR),
+                       out.ptr(o_cnt));
     SFM_HIP(hipGetLastError());
-    if (tm) SFM_HIP(hipEventRecord(c->ev[4], s));
-    hipLaunchKernelGGL(k_reg_refine, dim3((unsigned)V), dim3(RV_THREADS), 0, s, dX, dvs, dpt, dxy, (int32_t)H, cam,
-                       threshold, min_inliers, refit_rounds, max_nfev, dmP, dmCR, dcnt,
-                       reinterpret_cast<uint8_t *>(out + o_m2), reinterpret_cast<double *>(out),
-                       reinterpret_cast<double *>(out + o_R), reinterpret_cast<double *>(out + o_cost),
-                       reinterpret_cast<int32_t *>(out + o_ninl), reinterpret_cast<int32_t *>(out + o_hyp),
-                       reinterpret_cast<int32_t *>(out + o_bc), reinterpret_cast<int32_t *>(out + o_info),
-                       reinterpret_cast<uint8_t *>(out + o_mask));
+    SFM_TRY(tm.split(s));  // [3]: the fit-and-score kernel alone
+    hipLaunchKernelGGL(k_reg_refine, dim3((unsigned)V), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
+                       in.ptr(i_pt), in.ptr(i_xy), (int32_t)H, cam, threshold, min_inliers, refit_rounds, max_nfev,
+                       out.ptr(o_mP), out.ptr(o_mCR), out.ptr(o_cnt), out.ptr(o_m2), out.ptr(o_C), out.ptr(o_R),
+                       out.ptr(o_cost), out.ptr(o_ninl), out.ptr(o_hyp), out.ptr(o_bc), out.ptr(o_info),
+                       out.ptr(o_mask));
     SFM_HIP(hipGetLastError());
-    if (tm) SFM_HIP(hipEventRecord(c->ev[2], s));
+    SFM_TRY(tm.mark(s));
     // live views are copied out one run of consecutive views at a time, so that
     // what the host wrote for the views of info -1 stays
     for (int64_t v0 = 0; v0 < V;) {
@@ -785,38 +764,18 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
         int64_t v1 = v0;
         while (v1 < V && view_start[v1 + 1] - view_start[v1] >= 6) ++v1;
         const size_t nv = (size_t)(v1 - v0);
-        SFM_HIP(hipMemcpyAsync(C + 3 * v0, out + 3 * v0 * sizeof(double), nv * 3 * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-        SFM_HIP(hipMemcpyAsync(R + 9 * v0, out + o_R + 9 * v0 * sizeof(double), nv * 9 * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-        SFM_HIP(hipMemcpyAsync(cost + v0, out + o_cost + v0 * sizeof(double), nv * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-        SFM_HIP(hipMemcpyAsync(info + v0, out + o_info + v0 * sizeof(int32_t), nv * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        SFM_HIP(hipMemcpyAsync(n_inliers + v0, out + o_ninl + v0 * sizeof(int32_t), nv * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        SFM_HIP(hipMemcpyAsync(best_hyp + v0, out + o_hyp + v0 * sizeof(int32_t), nv * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-        SFM_HIP(hipMemcpyAsync(best_count + v0, out + o_bc + v0 * sizeof(int32_t), nv * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
+        SFM_TRY(out.download(C + 3 * v0, o_C, 3 * v0, 3 * nv, s));
+        SFM_TRY(out.download(R + 9 * v0, o_R, 9 * v0, 9 * nv, s));
+        SFM_TRY(out.download(cost + v0, o_cost, v0, nv, s));
+        SFM_TRY(out.download(info + v0, o_info, v0, nv, s));
+        SFM_TRY(out.download(n_inliers + v0, o_ninl, v0, nv, s));
+        SFM_TRY(out.download(best_hyp + v0, o_hyp, v0, nv, s));
+        SFM_TRY(out.download(best_count + v0, o_bc, v0, nv, s));
         const int64_t k0 = view_start[v0], k1 = view_start[v1];
-        SFM_HIP(hipMemcpyAsync(inlier + k0, out + o_mask + k0, (size_t)(k1 - k0), hipMemcpyDeviceToHost, s));
-        if (counts)
-            SFM_HIP(hipMemcpyAsync(counts + v0 * H, out + o_cnt + (size_t)(v0 * H) * sizeof(int32_t),
-                                   nv * (size_t)H * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (models)
-            SFM_HIP(hipMemcpyAsync(models + v0 * H * 12, out + o_mP + (size_t)(v0 * H) * 12 * sizeof(double),
-                                   nv * (size_t)H * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
+        if (counts) SFM_TRY(out.download(counts + v0 * H, o_cnt, v0 * H, nv * H, s));
+        if (models) SFM_TRY(out.download(models + v0 * H * 12, o_mP, v0 * H * 12, nv * H * 12, s));
         v0 = v1;
     }
-    if (tm) SFM_HIP(hipEventRecord(c->ev[3], s));
-    SFM_HIP(hipStreamSynchronize(s));
-    float a = 0, b = 0, d = 0, f = 0;
-    if (tm) (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-    if (tm) (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
-    if (tm) (void)hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
-    if (tm) (void)hipEventElapsedTime(&f, c->ev[1], c->ev[4]);
-    const double t4[4] = {a, b, d, f};  // [3]: the fit-and-score kernel alone
-    set_timings(t4, 4);
-    return 0;
+    return tm.finish(s);
 }

@@ -23,7 +23,7 @@
 // tracks have no length limit.
 #include <cmath>
 
-#include "sfm_common.hpp"
+#include "staging.hpp"
 // triangulate_point.hpp before lm_small.hpp, as in multiview.hip: the DLT body
 // is compiled as sfm_api.hip compiles it and returns sfm_triangulate_dlt's bits.
 #include "triangulate_point.hpp"
@@ -226,8 +226,6 @@ k_triangulate_tracks_robust(const double *__restrict__ Pg, int32_t n_cams, const
     if (angle_out) angle_out[t] = rt_angle(centres, obs_cam, s, e, inlier, x);
 }
 
-static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // Lanes per track when the caller leaves the choice open.  One lane per
 // track wastes nothing (the refit runs on one lane of a group while the
 // others idle), so it is the choice while the tracks alone fill the machine:
@@ -265,28 +263,23 @@ extern "C" int sfm_triangulate_tracks_robust(const double *P, int32_t n_cams, co
                   "lanes_per_track is 0 or a power of two up to 64");
     SFM_CHECK_ARG(centres || !angle, "angle needs centres");
     SFM_CHECK_ARG(track_start, "null pointer");
-    SFM_CHECK_ARG(track_start[0] == 0, "track_start does not start at 0");
+    SFM_TRY(check_csr(track_start, T, n_obs, "track_start", "observation"));
+    SFM_CHECK_ARG(n_obs == 0 || (obs_cam && obs_xy && P), "null pointer");
+    SFM_TRY(check_index(obs_cam, n_obs, n_cams, "camera index outside [0, n_cams)"));
+    if (T == 0) return 0;
+    SFM_CHECK_ARG(X && cost && n_inliers && best_pair && best_count && info && (inlier || n_obs == 0),
+                  "null pointer");
     int64_t max_track_pairs = 0, long_tracks = 0;
     double sum_pairs = 0.0;
     for (int64_t t = 0; t < T; ++t) {
         const int64_t n = track_start[t + 1] - track_start[t];
-        SFM_CHECK_ARG(n >= 0, "track_start decreases");
-        if (n >= 2) {
-            const double all = 0.5 * (double)n * (double)(n - 1);
-            const int64_t p = all < (double)max_pairs ? (int64_t)all : (int64_t)max_pairs;
-            max_track_pairs = p > max_track_pairs ? p : max_track_pairs;
-            sum_pairs += (double)p;
-            ++long_tracks;
-        }
+        if (n < 2) continue;
+        const double all = 0.5 * (double)n * (double)(n - 1);
+        const int64_t p = all < (double)max_pairs ? (int64_t)all : (int64_t)max_pairs;
+        max_track_pairs = p > max_track_pairs ? p : max_track_pairs;
+        sum_pairs += (double)p;
+        ++long_tracks;
     }
-    SFM_CHECK_ARG(track_start[T] == n_obs, "track_start does not end at the observation count");
-    SFM_CHECK_ARG(n_obs == 0 || (obs_cam && obs_xy && P), "null pointer");
-    // a camera index out of range is an error here, never a device read
-    for (int64_t k = 0; k < n_obs; ++k)
-        SFM_CHECK_ARG(obs_cam[k] >= 0 && obs_cam[k] < n_cams, "camera index outside [0, n_cams)");
-    if (T == 0) return 0;
-    SFM_CHECK_ARG(X && cost && n_inliers && best_pair && best_count && info && (inlier || n_obs == 0),
-                  "null pointer");
     int G = lanes_per_track ? lanes_per_track
                             : auto_lanes(T, long_tracks ? sum_pairs / (double)long_tracks : 0.0, max_track_pairs);
     while (G > 1 && (T + (256 / G) - 1) / (256 / G) > (int64_t)0x7fffffff) G /= 2;
@@ -295,59 +288,41 @@ extern "C" int sfm_triangulate_tracks_robust(const double *P, int32_t n_cams, co
     while ((1 << LG) < G) ++LG;
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    // buf[0]: track_start | obs_xy | obs_cam | centres | P
-    // buf[1]: X | cost | angle | info | n_inliers | best_pair | best_count | inlier
-    const size_t b_ts = (size_t)(T + 1) * sizeof(int64_t), b_xy = (size_t)n_obs * sizeof(double2),
-                 b_cam = (size_t)n_obs * sizeof(int32_t), b_x = (size_t)T * 3 * sizeof(double),
-                 b_c = (size_t)n_cams * 3 * sizeof(double), b_p = (size_t)n_cams * 12 * sizeof(double),
-                 b_d = (size_t)T * sizeof(double), b_i = (size_t)T * sizeof(int32_t);
-    const size_t o_xy = up256(b_ts), o_cam = o_xy + up256(b_xy), o_c = o_cam + up256(b_cam), o_p = o_c + up256(b_c),
-                 in_bytes = o_p + up256(b_p);
-    const size_t o_cost = up256(b_x), o_ang = o_cost + up256(b_d), o_info = o_ang + up256(b_d),
-                 o_ninl = o_info + up256(b_i), o_pair = o_ninl + up256(b_i), o_cnt = o_pair + up256(b_i),
-                 o_mask = o_cnt + up256(b_i), out_bytes = o_mask + up256((size_t)n_obs);
-    int rc;
-    if ((rc = c->buf[0].reserve(in_bytes)) || (rc = c->buf[1].reserve(out_bytes))) return rc;
-    char *in = c->buf[0].as<char>(), *out = c->buf[1].as<char>();
+    Pack in(c->buf[0]), out(c->buf[1]);
+    const auto i_ts = in.add<int64_t>(T + 1);
+    const auto i_xy = in.add<double2>(n_obs);
+    const auto i_cam = in.add<int32_t>(n_obs);
+    const auto i_c = in.add<double>(3 * (size_t)n_cams), i_p = in.add<double>(12 * (size_t)n_cams);
+    const auto o_x = out.add<double>(3 * T), o_cost = out.add<double>(T), o_ang = out.add<double>(T);
+    const auto o_info = out.add<int32_t>(T), o_ninl = out.add<int32_t>(T);
+    const auto o_pair = out.add<int32_t>(T), o_cnt = out.add<int32_t>(T);
+    const auto o_mask = out.add<uint8_t>(n_obs);
+    SFM_TRY(in.reserve());
+    SFM_TRY(out.reserve());
     hipStream_t s = c->stream;
-    const bool tm = call_timing();  // HIP events only when asked (each costs the stream us)
-    if (tm) SFM_HIP(hipEventRecord(c->ev[0], s));
-    SFM_HIP(hipMemcpyAsync(in, track_start, b_ts, hipMemcpyHostToDevice, s));
-    if (n_obs) {
-        SFM_HIP(hipMemcpyAsync(in + o_xy, obs_xy, b_xy, hipMemcpyHostToDevice, s));
-        SFM_HIP(hipMemcpyAsync(in + o_cam, obs_cam, b_cam, hipMemcpyHostToDevice, s));
-    }
-    if (centres && n_cams) SFM_HIP(hipMemcpyAsync(in + o_c, centres, b_c, hipMemcpyHostToDevice, s));
-    if (n_cams) SFM_HIP(hipMemcpyAsync(in + o_p, P, b_p, hipMemcpyHostToDevice, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[1], s));
-    const dim3 grid(ceil_div(T, 256 / G)), block(256);
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(in.upload(i_ts, track_start, s));
+    SFM_TRY(in.upload(i_xy, obs_xy, s));
+    SFM_TRY(in.upload(i_cam, obs_cam, s));
+    SFM_TRY(in.upload(i_c, centres, s));
+    SFM_TRY(in.upload(i_p, P, s));
+    SFM_TRY(tm.mark(s));
     auto kernel = n_cams <= MV_LDS_CAMS ? k_triangulate_tracks_robust<true> : k_triangulate_tracks_robust<false>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, reinterpret_cast<const double *>(in + o_p), n_cams,
-                       centres ? reinterpret_cast<const double *>(in + o_c) : nullptr,
-                       reinterpret_cast<const int64_t *>(in), reinterpret_cast<const int32_t *>(in + o_cam),
-                       reinterpret_cast<const double2 *>(in + o_xy), T, threshold * threshold, max_pairs, min_inliers,
-                       max_nfev, LG, reinterpret_cast<double *>(out), reinterpret_cast<double *>(out + o_cost),
-                       reinterpret_cast<int32_t *>(out + o_ninl), reinterpret_cast<uint8_t *>(out + o_mask),
-                       reinterpret_cast<int32_t *>(out + o_pair), reinterpret_cast<int32_t *>(out + o_cnt),
-                       reinterpret_cast<int32_t *>(out + o_info),
-                       angle ? reinterpret_cast<double *>(out + o_ang) : nullptr);
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(T, 256 / G)), dim3(256), 0, s, in.ptr(i_p), n_cams,
+                       centres ? in.ptr(i_c) : nullptr, in.ptr(i_ts), in.ptr(i_cam), in.ptr(i_xy), T,
+                       threshold * threshold, max_pairs, min_inliers, max_nfev, LG, out.ptr(o_x), out.ptr(o_cost),
+                       out.ptr(o_ninl), out.ptr(o_mask), out.ptr(o_pair), out.ptr(o_cnt), out.ptr(o_info),
+                       angle ? out.ptr(o_ang) : nullptr);
     SFM_HIP(hipGetLastError());
-    if (tm) SFM_HIP(hipEventRecord(c->ev[2], s));
-    SFM_HIP(hipMemcpyAsync(X, out, b_x, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(cost, out + o_cost, b_d, hipMemcpyDeviceToHost, s));
-    if (angle) SFM_HIP(hipMemcpyAsync(angle, out + o_ang, b_d, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(info, out + o_info, b_i, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(n_inliers, out + o_ninl, b_i, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(best_pair, out + o_pair, b_i, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(best_count, out + o_cnt, b_i, hipMemcpyDeviceToHost, s));
-    if (n_obs) SFM_HIP(hipMemcpyAsync(inlier, out + o_mask, (size_t)n_obs, hipMemcpyDeviceToHost, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[3], s));
-    SFM_HIP(hipStreamSynchronize(s));
-    float a = 0, b = 0, d = 0;
-    if (tm) (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-    if (tm) (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
-    if (tm) (void)hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
-    const double t4[4] = {a, b, d, b};
-    set_timings(t4, 4);
-    return 0;
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(out.download(X, o_x, s));
+    SFM_TRY(out.download(cost, o_cost, s));
+    SFM_TRY(out.download(angle, o_ang, s));
+    SFM_TRY(out.download(info, o_info, s));
+    SFM_TRY(out.download(n_inliers, o_ninl, s));
+    SFM_TRY(out.download(best_pair, o_pair, s));
+    SFM_TRY(out.download(best_count, o_cnt, s));
+    SFM_TRY(out.download(inlier, o_mask, s));
+    return tm.finish(s);
 }

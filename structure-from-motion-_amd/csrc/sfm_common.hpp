@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,9 @@ bool call_timing();
             return SFM_ERR_ARG;                    \
         }                                          \
     } while (0)
+
+// a call that reports its own error: pass its status on
+#define SFM_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)
 
 // Device scratch that only grows; freed at thread exit.
 struct DevBuf {
@@ -114,5 +118,11 @@ struct ThreadCtx {
 ThreadCtx *thread_ctx(int device);
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// an integer switch from the environment; unset or empty gives dflt
+inline int env_int(const char *name, int dflt) {
+    const char *v = std::getenv(name);
+    return v && *v ? std::atoi(v) : dflt;
+}
 
 }  // namespace sfm

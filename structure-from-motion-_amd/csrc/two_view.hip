@@ -4,7 +4,7 @@
 // taken in one launch; the host picks the first maximum.
 #include <cstring>
 
-#include "sfm_common.hpp"
+#include "staging.hpp"
 #include "triangulate_point.hpp"
 
 namespace sfm {
@@ -119,17 +119,17 @@ extern "C" int sfm_two_view_select(const double *P1, const double *P2s, const do
     std::memcpy(P.p2, P2s, (size_t)M * 12 * sizeof(double));
     fill_cams(cam, R1, C1, Rs, Cs, M);
     hipStream_t s = c->stream;
-    const bool tm = call_timing();  // HIP events only when asked (each costs the stream us)
-    if (tm) SFM_HIP(hipEventRecord(c->ev[0], s));
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
     SFM_HIP(hipMemcpyAsync(c->buf[0].p, x1, pb, hipMemcpyHostToDevice, s));
     SFM_HIP(hipMemcpyAsync(c->buf[1].p, x2, pb, hipMemcpyHostToDevice, s));
     SFM_HIP(hipMemsetAsync(c->buf[3].p, 0, cb, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[1], s));
+    SFM_TRY(tm.mark(s));
     hipLaunchKernelGGL(k_two_view_select, dim3(ceil_div(N, 256), M), dim3(256), 0, s, P, cam,
                        c->buf[0].as<double2>(), c->buf[1].as<double2>(), N, c->buf[2].as<double>(),
                        c->buf[3].as<unsigned long long>());
     SFM_HIP(hipGetLastError());
-    if (tm) SFM_HIP(hipEventRecord(c->ev[2], s));
+    SFM_TRY(tm.mark(s));
     unsigned long long dc[TV_MAX];
     SFM_HIP(hipMemcpyAsync(dc, c->buf[3].p, cb, hipMemcpyDeviceToHost, s));
     SFM_HIP(hipStreamSynchronize(s));
@@ -137,15 +137,7 @@ extern "C" int sfm_two_view_select(const double *P1, const double *P2s, const do
     // only the winner's points come back, all of them only on request
     SFM_HIP(hipMemcpyAsync(X_best, c->buf[2].as<char>() + (size_t)*best * xb, xb, hipMemcpyDeviceToHost, s));
     if (X_all) SFM_HIP(hipMemcpyAsync(X_all, c->buf[2].p, (size_t)M * xb, hipMemcpyDeviceToHost, s));
-    if (tm) SFM_HIP(hipEventRecord(c->ev[3], s));
-    SFM_HIP(hipStreamSynchronize(s));
-    float a = 0, b = 0, d = 0;
-    if (tm) (void)hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
-    if (tm) (void)hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
-    if (tm) (void)hipEventElapsedTime(&d, c->ev[2], c->ev[3]);
-    const double t[4] = {a, b, d, b};
-    set_timings(t, 4);
-    return 0;
+    return tm.finish(s);
 }
 
 extern "C" int sfm_cheirality_count(const double *R1, const double *C1, const double *Rs, const double *Cs,
