@@ -366,6 +366,63 @@ int sfm_register_views(const double *K, const double *X, int64_t n_pts, const in
                        int device);
 
 /* ---------------------------------------------------------------------
+ * Batched pair verification: 8-point F-RANSAC and a least-squares refit for
+ * every image pair in one call, under one convention, x2^T F x1 = 0 (the
+ * reference verifies one pair per call, Wrapper_dev.py:69-123, with a design
+ * row for x1^T F x2 = 0 under a score for x2^T F x1 = 0, which the drop-ins
+ * keep bit for bit; differs on purpose).
+ * The P pairs are CSR rows: pair p owns correspondences [pair_start[p],
+ * pair_start[p+1]) of x1 and x2 (n_corr x 2 each: pixel coordinates in the
+ * pair's first and second image); pair_start has P + 1 entries, starts at 0,
+ * never decreases and ends at n_corr.  samples (P x H x 8): each entry a
+ * position inside its pair, in [0, n_p), the eight of a hypothesis distinct;
+ * ignored for pairs of n_p < 8.  A violation is SFM_ERR_ARG, found on the host
+ * before anything is launched.
+ * Hypothesis: Hartley normalisation of the eight points on each side (centroid
+ * to the origin, mean distance sqrt 2), the design row [c a, c b, c, d a, d b,
+ * d, a, b, 1] with (a, b) the normalised first point and (c, d) the second,
+ * the null vector of the 8 x 9 system as F^ (row-major), projected to rank 2,
+ * F = T2^T F^ T1, scaled to unit Frobenius norm with the sign that makes the
+ * entry of largest magnitude (the first such in row-major order) positive; no
+ * division by F[2,2].  One whose model is not finite scores 0.
+ * A correspondence is an inlier of F where, with e = x2^T F x1 and den =
+ * (F x1)_0^2 + (F x1)_1^2 + (F^T x2)_0^2 + (F^T x2)_1^2, den > 0 and e e <
+ * threshold^2 den: the squared Sampson distance against the squared threshold,
+ * without a division or a square root (the fp64 expression decides).  The
+ * winner has the most inliers, then the earliest place in the table.
+ * Refit: the normalised least-squares fit over the current inliers (the same
+ * design, N x 9, Hartley statistics of the inliers on each side; Givens QR to
+ * a 9 x 9 triangular factor, its right singular vector of the least singular
+ * value by one-sided Jacobi), then rank 2, denormalisation, scale and sign as
+ * for a hypothesis; every correspondence of the pair is scored against it, and
+ * (count, then smaller cost) replaces the current state only if it is not
+ * worse; up to refit_rounds rounds, ending early when the mask does not change,
+ * when the new state is worse or when fewer than 8 inliers remain.  So
+ * n_inliers >= best_count.
+ * Outputs per pair: F (P x 9, row-major), cost (the sum of the final inliers'
+ * squared Sampson distances e e / den), n_inliers, best_hyp (-1 without one),
+ * best_count, info: 1 the refit ended on an unchanged mask, 2 it ended on a
+ * worse state or refit_rounds ran out, 0 refit_rounds = 0, -1 n_p < 8 (F = 0,
+ * nothing an inlier; nothing of the pair is read on or from the device), -2 no
+ * finite hypothesis (the same outputs), -3 best_count < min_inliers (the
+ * winning hypothesis's F, mask, count and cost, no refit).
+ * Per correspondence: inlier (n_corr), 1 or 0.  Nullable: counts (P x H) the
+ * inliers per hypothesis, models (P x H x 9) the hypotheses; both zero for a
+ * pair of n_p < 8.
+ * threshold is in pixels, finite and > 0; H >= 1; min_inliers >= 8;
+ * refit_rounds >= 0.  No sum depends on the batch: a pair's outputs are the
+ * same bits alone, in any batch and at any place in it.  Two launches and one
+ * synchronisation whatever P is; P == 0, or no pair of eight correspondences,
+ * returns without touching a device.  sfm_last_timings: upload, both kernels,
+ * download, the fit-and-score kernel alone.
+ * ------------------------------------------------------------------- */
+int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const double *x1, const double *x2, int64_t n_corr,
+                     const int32_t *samples, int64_t H, double threshold, int32_t min_inliers,
+                     int32_t refit_rounds, double *F, double *cost, int32_t *n_inliers, int32_t *best_hyp,
+                     int32_t *best_count, int32_t *info, uint8_t *inlier, int32_t *counts, double *models,
+                     int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

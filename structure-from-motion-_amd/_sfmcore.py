@@ -105,6 +105,8 @@ SIGNATURES = [
     ("sfm_register_views", _c, [_d, _d, _i, _i64, _i, _i32, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32,
                                 ctypes.c_int32, ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32, _d,
                                 _c]),
+    ("sfm_verify_pairs", _c, [_i64, _i, _d, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _d,
+                              _d, _i32, _i32, _i32, _i32, _u8, _i32, _d, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -818,25 +820,98 @@ def register_samples(counts, H, seed):
     numpy.random.default_rng(seed) -- integers(0, n_v, (H, 6)), the rows that
     hold a duplicate redrawn until none do -- so its table does not depend on
     the other views; a view of n_v < 6 gets zeros."""
+    return _sample_tables(counts, H, seed, 6, "register_samples")
+
+
+def _sample_tables(counts, H, seed, k, who):
+    """(len(counts), H, k) int32: row v from child v of the seed, k distinct
+    positions in [0, counts[v]) per hypothesis, zeros where counts[v] < k"""
     counts = np.asarray(counts, dtype=np.int64).reshape(-1)
     H = int(H)
     if H < 1:
-        raise ValueError("register_samples: H must be at least 1")
-    out = np.zeros((len(counts), H, 6), dtype=np.int32)
+        raise ValueError(f"{who}: H must be at least 1")
+    out = np.zeros((len(counts), H, k), dtype=np.int32)
     root = np.random.SeedSequence(seed)
     for v, n in enumerate(counts):
-        if n < 6:
+        if n < k:
             continue
         # child v of the seed, whatever the number of views
         rng = np.random.default_rng(np.random.SeedSequence(root.entropy, spawn_key=(v,)))
-        t = rng.integers(0, n, (H, 6))
+        t = rng.integers(0, n, (H, k))
         while True:
             s = np.sort(t, axis=1)
             dup = np.where((s[:, 1:] == s[:, :-1]).any(axis=1))[0]
             if not len(dup):
                 break
-            t[dup] = rng.integers(0, n, (len(dup), 6))
+            t[dup] = rng.integers(0, n, (len(dup), k))
         out[v] = t
+    return out
+
+
+def pair_samples(counts, H, seed):
+    """The 8-point sample table of verify_pairs for pairs of ``counts``
+    correspondences: (P, H, 8) int32, drawn as register_samples draws -- pair p
+    from child p of numpy.random.default_rng(seed), the rows that hold a
+    duplicate redrawn until none do, so a pair's table does not depend on the
+    other pairs; a pair of n_p < 8 gets zeros."""
+    return _sample_tables(counts, H, seed, 8, "pair_samples")
+
+
+def verify_pairs(pair_start, x1, x2, samples, threshold=2.5, min_inliers=8, refit_rounds=3, want_counts=False,
+                 want_models=False):
+    """Batched pair verification (sfm_verify_pairs): for every image pair,
+    8-point F-RANSAC over the host-drawn ``samples`` (P, H, 8; pair_samples)
+    under x2^T F x1 = 0 with the Sampson distance as the inlier rule, the
+    winner refitted to its consensus set by normalised least squares in up to
+    ``refit_rounds`` rounds, and the inlier mask of the pair's correspondences.
+    The pairs are CSR rows: pair p owns x1 / x2[pair_start[p]:pair_start[p + 1]],
+    pixel coordinates in its first and second image.
+    Returns (F (P, 3, 3) of unit Frobenius norm, cost (P,) sum of the final
+    inliers' squared Sampson distances, n_inliers (P,) int32, inlier (n_corr,)
+    bool, best_hyp (P,) int32, best_count (P,) int32, info (P,) int32: 1 the
+    refit ended on an unchanged mask, 2 on a worse state or out of rounds, 0 no
+    refit asked for, -1 fewer than eight correspondences, -2 no finite
+    hypothesis, -3 best_count < min_inliers), then counts (P, H) int32 with
+    want_counts and models (P, H, 3, 3) with want_models.  The arguments are
+    checked before a device is looked for; P = 0, or no pair of eight
+    correspondences, returns without one."""
+    ps = np.ascontiguousarray(pair_start, dtype=np.int64).reshape(-1)
+    x1 = _f64(x1).reshape(-1, 2)
+    x2 = _f64(x2).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    if len(ps) < 1 or len(x1) != len(x2):
+        raise ValueError("verify_pairs: pair_start needs P + 1 entries and x1, x2 one row per correspondence")
+    P = len(ps) - 1
+    if samples.ndim != 3 or samples.shape[0] != P or samples.shape[2] != 8 or samples.shape[1] < 1:
+        raise ValueError("verify_pairs: samples must be (P, H, 8) with H >= 1")
+    H = samples.shape[1]
+    threshold = float(threshold)
+    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 8 or int(refit_rounds) < 0
+           or ps[0] != 0 or bool(np.any(np.diff(ps) < 0)) or ps[-1] != len(x1))
+    if not bad:
+        n_p = np.diff(ps)
+        live = n_p >= 8
+        if live.any():
+            s = samples[live]
+            srt = np.sort(s, axis=2)
+            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_p[live]).any()
+                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
+            if not bad:
+                require_device()
+    F, cost = np.zeros((P, 9)), np.zeros(P)
+    n_inl, hyp, count, info = (np.zeros(P, dtype=np.int32) for _ in range(4))
+    inlier = np.zeros(len(x1), dtype=np.uint8)
+    counts = np.zeros((P, H), dtype=np.int32) if want_counts else None
+    models = np.zeros((P, H, 9)) if want_models else None
+    _check(_lib.sfm_verify_pairs(
+        _p(ps, _i64), P, _p(x1), _p(x2), len(x1), _p(samples, _i32), H, threshold, int(min_inliers),
+        int(refit_rounds), _p(F), _p(cost), _p(n_inl, _i32), _p(hyp, _i32), _p(count, _i32), _p(info, _i32),
+        _p(inlier, _u8), _p(counts, _i32) if want_counts else None, _p(models) if want_models else None, DEVICE))
+    out = (F.reshape(P, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info)
+    if want_counts:
+        out += (counts,)
+    if want_models:
+        out += (models.reshape(P, H, 3, 3),)
     return out
 
 

@@ -1,0 +1,547 @@
+// Batched pair verification: the epipolar geometry of every image pair of a
+// store in one call.  Every pair brings its correspondences (CSR over pairs)
+// and a host-drawn table of 8-point samples; one call returns, per pair, the
+// RANSAC winner, the fundamental matrix refitted to its consensus set and the
+// inlier mask of the pair's correspondences -- the flags every later stage of
+// the pipeline reads.  The reference verifies one pair per call
+// (Wrapper_dev.py:69-123) with a design row for x1^T F x2 = 0 under a
+// denormalisation and a score for x2^T F x1 = 0; the drop-ins keep that bit for
+// bit.  This entry point uses x2^T F x1 = 0 throughout, a unit-norm model and
+// the Sampson distance (epi_sampson.hpp).  Differs on purpose.
+//
+//   k_vp_fit_score  flat grid over (pair, hypothesis tile) from a host prefix
+//                   table.  Fit: a hypothesis belongs to 8 lanes, one design row
+//                   each (vp_fit_group8).  Score: the pair's correspondences are
+//                   staged through LDS in tiles of 1024, a wave per hypothesis,
+//                   ballot popcount of the inlier rule.
+//   k_vp_refit      one workgroup per pair: winner (most inliers, then the
+//                   earliest), its mask, then rounds of the normalised
+//                   least-squares fit over the current inliers (Hartley sums,
+//                   per-thread Givens QR of the N x 9 design, a tree merge of
+//                   the 9 x 9 factors in LDS, one lane's 9-column Jacobi), a
+//                   re-score of the whole pair and the not-worse test.
+//
+// Every sum runs in a fixed order over quantities of the pair alone (strided
+// per-thread partial sums, a 64-lane butterfly, the two wave results added);
+// the factors merge along a fixed tree; counts are integers.  A pair's outputs
+// therefore do not depend on the batch it is in.
+#include <cmath>
+#include <cstring>
+
+#include "dlt_general.hpp"
+#include "epi_sampson.hpp"
+#include "select.hpp"
+#include "staging.hpp"
+
+#pragma clang fp contract(off)
+
+namespace sfm {
+
+constexpr int VP_THREADS = 256;                // fit and score
+constexpr int VP_WAVES = VP_THREADS / 64;
+constexpr int VP_FIT = VP_THREADS / 8;         // hypotheses fitted per pass
+constexpr int VP_HT = 64;                      // most hypotheses per workgroup
+constexpr int VP_TILE = 1024;                  // correspondences per LDS tile (32 KiB)
+constexpr int VP_RT = FG_THREADS;              // refit: 128 threads of 45 doubles, 45 KiB of LDS
+constexpr int VP_RW = VP_RT / 64;
+static_assert(VP_RW == 2, "vp_wg_sum adds two wave results");
+
+// blk_start (n_live + 1): the first block of each live pair (n_p >= 8); tab
+// (n_live x 2): the pair and the hypotheses per block chosen for it.  models
+// (P x H x 9); counts (P x H), 0 for a model that is not finite.
+__global__ void __launch_bounds__(VP_THREADS)
+k_vp_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1,
+               const double2 *__restrict__ x2, const int32_t *__restrict__ samples, int32_t H,
+               const int32_t *__restrict__ blk_start, const int32_t *__restrict__ tab, int32_t n_live, double thr,
+               double *__restrict__ models, int32_t *__restrict__ counts) {
+    __shared__ double sF[VP_HT][9];
+    __shared__ double2 s1[VP_TILE];
+    __shared__ double2 s2[VP_TILE];
+    __shared__ int32_t sFin[VP_HT], sCnt[VP_HT];
+    const int tid = threadIdx.x;
+    // the live pair of this block: the last j with blk_start[j] <= blockIdx.x
+    int lo = 0, hi = n_live - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk_start[mid] <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const int32_t p = tab[2 * lo], ht = tab[2 * lo + 1];
+    const int32_t hb = ((int32_t)blockIdx.x - blk_start[lo]) * ht;
+    const int nh = min(ht, H - hb);
+    const int64_t ps = pair_start[p];
+    const int n = (int)(pair_start[p + 1] - ps);
+    const int64_t row0 = (int64_t)p * H + hb;
+
+    // ---- fit: 32 hypotheses a pass, 8 lanes each
+    const int k = tid & 7;
+    for (int pass = 0; pass * VP_FIT < nh; ++pass) {
+        const int hl = pass * VP_FIT + (tid >> 3);
+        const bool valid = hl < nh;  // the same for the 8 lanes of a group
+        double2 a = make_double2(0.0, 0.0), b = a;
+        if (valid) {
+            const int64_t c = ps + samples[(row0 + hl) * 8 + k];
+            a = x1[c];
+            b = x2[c];
+        }
+        double F[9];
+        vp_fit_group8(a.x, a.y, b.x, b.y, F);
+        bool fin = true;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) fin = fin && isfinite(F[j]);
+        if (valid) {
+            double fk = F[0];
+#pragma unroll
+            for (int j = 1; j < 8; ++j) fk = k == j ? F[j] : fk;
+            sF[hl][k] = fk;
+            models[(row0 + hl) * 9 + k] = fk;
+            if (k == 0) {
+                sF[hl][8] = F[8];
+                models[(row0 + hl) * 9 + 8] = F[8];
+                sFin[hl] = fin ? 1 : 0;
+                sCnt[hl] = 0;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- score: a wave per hypothesis, the pair's tile shared by all of them
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const double thr2 = thr * thr;
+    for (int base = 0; base < n; base += VP_TILE) {
+        const int nt = min(VP_TILE, n - base);
+        for (int i = tid; i < nt; i += VP_THREADS) {
+            s1[i] = x1[ps + base + i];
+            s2[i] = x2[ps + base + i];
+        }
+        __syncthreads();
+        for (int hl = wave; hl < nh; hl += VP_WAVES) {
+            if (!sFin[hl]) continue;
+            double F[9];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) F[j] = sF[hl][j];
+            int cnt = 0;
+            for (int j = 0; j < nt; j += 64) {
+                const int i = j + lane;
+                bool in = false;
+                if (i < nt) {
+                    const double2 q1 = s1[i], q2 = s2[i];
+                    double e2, den;
+                    in = vp_inlier(F, q1.x, q1.y, q2.x, q2.y, thr2, e2, den);
+                }
+                cnt += __popcll(__ballot(in));
+            }
+            if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
+        }
+        __syncthreads();
+    }
+    if (tid < nh) counts[row0 + tid] = sFin[tid] ? sCnt[tid] : 0;
+}
+
+// ------------------------------------------------------------------ phase 2
+// Fixed-order sum of NV values over the workgroup: a 64-lane butterfly (both
+// partners add the same pair, so every lane holds the same bits), then the two
+// wave results.  red: VP_RW x NV.
+template <int NV>
+__device__ __forceinline__ void vp_wg_sum(double (&x)[NV], double (*red)[NV]) {
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) x[j] += __shfl_xor(x[j], w);
+    __syncthreads();  // the last use of red is over
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) red[threadIdx.x >> 6][j] = x[j];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) x[j] = red[0][j] + red[1][j];
+}
+
+struct VpPair {
+    const double2 *x1, *x2;  // the pair's first correspondence
+    int n;
+};
+
+// mask[i] = the inlier rule under F for the pair's correspondence i; count and
+// the inliers' squared Sampson distances summed (thread t owns i = t, t + 128, ...)
+__device__ __forceinline__ void vp_mask(const VpPair &w, const double *F, double thr2, uint8_t *mask, int &count,
+                                        double &cost, double (*red)[4]) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < w.n; i += VP_RT) {
+        const double2 p = w.x1[i], q = w.x2[i];
+        double e2, den;
+        const bool in = vp_inlier(F, p.x, p.y, q.x, q.y, thr2, e2, den);
+        mask[i] = in ? 1 : 0;
+        if (in) {
+            acc[0] += 1.0;
+            acc[1] += e2 / den;
+        }
+    }
+    vp_wg_sum<4>(acc, red);
+    count = (int)acc[0];
+    cost = acc[1];
+}
+
+// jacobi_onesided<9, 9, 40> and weakest_column on a matrix in LDS, for one
+// lane: a[9 j + i] is column j, row i; V (9 x 9, row-major) accumulates the
+// rotations.  The same rotation rule, threshold and sweep cap; held in
+// registers, the two matrices alone are 324 VGPRs and the kernel spills.
+// Returns the column of the smallest norm (the first of equals).
+__device__ __forceinline__ int vp_jacobi9(double *a, double *V) {
+    for (int i = 0; i < 81; ++i) V[i] = i % 10 == 0 ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < 8; ++p) {
+            double x[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) x[k] = a[9 * p + k];
+            for (int q = p + 1; q < 9; ++q) {
+                double y[9];
+                double al = 0, be = 0, ga = 0;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    y[k] = a[9 * q + k];
+                    al += x[k] * x[k];
+                    be += y[k] * y[k];
+                    ga += x[k] * y[k];
+                }
+                const double r = fabs(ga) / sqrt(al * be);
+                if (ga != 0.0 && r > 1e-15) {
+                    off = fmax(off, r);
+                    const double zeta = (be - al) / (2.0 * ga);
+                    const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) {
+                        const double u = x[k], v = y[k];
+                        x[k] = cs * u - sn * v;
+                        a[9 * q + k] = sn * u + cs * v;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) {
+                        const double u = V[9 * k + p], v = V[9 * k + q];
+                        V[9 * k + p] = cs * u - sn * v;
+                        V[9 * k + q] = sn * u + cs * v;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) a[9 * p + k] = x[k];
+        }
+        if (off < 1e-15) break;
+    }
+    int best = 0;
+    double bn = 0.0;
+    for (int j = 0; j < 9; ++j) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s += a[9 * j + k] * a[9 * j + k];
+        if (j == 0 || s < bn) { bn = s; best = j; }
+    }
+    return best;
+}
+
+// The normalised least-squares fit over the masked correspondences (n_in of
+// them, at least 8): Hartley statistics of the inliers on each side, the N x 9
+// design reduced to a 9 x 9 triangular factor by per-thread Givens rotations
+// and the LDS tree merge of k_dlt_general, then thread 0's one-sided Jacobi
+// for the right singular vector of the least singular value and vp_finish.
+// F to every thread, through sFn.
+__device__ __forceinline__ void vp_refit(const VpPair &w, const uint8_t *mask, int n_in, double (*red)[4],
+                                         double (*Rs)[45], double *sFn, double (&F)[9]) {
+    const int t = threadIdx.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = t; i < w.n; i += VP_RT) {
+        if (!mask[i]) continue;
+        const double2 p = w.x1[i], q = w.x2[i];
+        s[0] += p.x; s[1] += p.y; s[2] += q.x; s[3] += q.y;
+    }
+    vp_wg_sum<4>(s, red);
+    const double N = (double)n_in;
+    const double m1x = s[0] / N, m1y = s[1] / N, m2x = s[2] / N, m2y = s[3] / N;
+    double d[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = t; i < w.n; i += VP_RT) {
+        if (!mask[i]) continue;
+        const double2 p = w.x1[i], q = w.x2[i];
+        const double ax = p.x - m1x, ay = p.y - m1y, bx = q.x - m2x, by = q.y - m2y;
+        d[0] += sqrt(ax * ax + ay * ay);
+        d[1] += sqrt(bx * bx + by * by);
+    }
+    vp_wg_sum<4>(d, red);
+    Hartley h1, h2;
+    h1.s = 1.4142135623730951 / (d[0] / N + 1e-8);
+    h2.s = 1.4142135623730951 / (d[1] / N + 1e-8);
+    h1.ox = -h1.s * m1x; h1.oy = -h1.s * m1y; h2.ox = -h2.s * m2x; h2.oy = -h2.s * m2y;
+    double R[9][9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+        for (int j = 0; j < 9; ++j) R[i][j] = 0.0;
+    for (int i = t; i < w.n; i += VP_RT) {
+        if (!mask[i]) continue;
+        const double2 p = w.x1[i], q = w.x2[i];
+        double row[9];
+        vp_row(h1.s * p.x + h1.ox, h1.s * p.y + h1.oy, h2.s * q.x + h2.ox, h2.s * q.y + h2.oy, row);
+        givens_absorb(R, row);
+    }
+    for (int wd = VP_RT / 2; wd > 0; wd >>= 1) {
+        if (t >= wd && t < 2 * wd) {
+            int k = 0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+#pragma unroll
+                for (int j = i; j < 9; ++j) Rs[t][k++] = R[i][j];
+        }
+        __syncthreads();
+        if (t < wd) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                double row[9];
+#pragma unroll
+                for (int j = 0; j < 9; ++j) row[j] = 0.0;
+#pragma unroll
+                for (int j = i; j < 9; ++j) row[j] = Rs[t + wd][i * 9 - i * (i - 1) / 2 + (j - i)];
+                givens_absorb(R, row);
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        // the merge is over: its LDS now holds the factor's columns and V
+        double *a = &Rs[0][0], *V = a + 81;  // a[9 col + row], V[9 row + col]
+#pragma unroll
+        for (int c = 0; c < 9; ++c)
+#pragma unroll
+            for (int r = 0; r < 9; ++r) a[9 * c + r] = r <= c ? R[r][c] : 0.0;
+        const int j = vp_jacobi9(a, V);
+        double f[9], Fn[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = V[9 * k + j];
+        vp_finish(f, h1, h2, Fn);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sFn[k] = Fn[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 9; ++k) F[k] = sFn[k];
+}
+
+// One workgroup per pair.  mask2: scratch of n_corr bytes.  Pairs of fewer than
+// eight correspondences are the host's (info -1): nothing of them is read.
+__global__ void __launch_bounds__(VP_RT)
+k_vp_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1, const double2 *__restrict__ x2,
+           int32_t H, double thr, int32_t min_inliers, int32_t refit_rounds, const double *__restrict__ models,
+           const int32_t *__restrict__ counts, uint8_t *mask2, double *__restrict__ F_out,
+           double *__restrict__ cost_out, int32_t *__restrict__ n_inl_out, int32_t *__restrict__ hyp_out,
+           int32_t *__restrict__ count_out, int32_t *__restrict__ info_out, uint8_t *inlier) {
+    __shared__ int32_t sc[VP_RW];
+    __shared__ int64_t sh[VP_RW];
+    __shared__ int32_t sFirst;
+    __shared__ double red[VP_RW][4];
+    __shared__ double sFn[9];
+    __shared__ double Rs[VP_RT][45];
+    const int tid = threadIdx.x;
+    const int64_t p = blockIdx.x;
+    const int64_t ps = pair_start[p];
+    const int n = (int)(pair_start[p + 1] - ps);
+    if (n < 8) return;
+    const VpPair w{x1 + ps, x2 + ps, n};
+    uint8_t *mask = inlier + ps, *trial = mask2 + ps;
+    const double thr2 = thr * thr;
+
+    int32_t bc;
+    int64_t bh;
+    if (tid == 0) sFirst = H;
+    wg_select_best<VP_RT>(counts + p * H, H, sc, sh, bc, bh);  // holds a barrier
+    if (bh < 0) {  // every count is 0: the earliest finite hypothesis, if any
+        for (int32_t h = tid; h < H; h += VP_RT) {
+            const double *m = models + (p * H + h) * 9;
+            bool fin = true;
+            for (int j = 0; j < 9; ++j) fin = fin && isfinite(m[j]);
+            if (fin) {
+                atomicMin(&sFirst, h);
+                break;
+            }
+        }
+        __syncthreads();
+        bh = sFirst < H ? sFirst : -1;
+        bc = 0;
+    }
+    double F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, cost = 0.0;
+    int info = -2, n_inl = 0;
+    if (bh < 0) {
+        for (int i = tid; i < n; i += VP_RT) mask[i] = 0;
+    } else {
+        const double *m = models + (p * H + bh) * 9;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) F[j] = m[j];
+        vp_mask(w, F, thr2, mask, n_inl, cost, red);
+        info = -3;
+        if (bc >= min_inliers) {
+            info = refit_rounds > 0 ? 2 : 0;
+            for (int round = 0; round < refit_rounds; ++round) {
+                if (n_inl < 8) break;
+                // (a thread reads and writes the masks at its own i = t, t + 128, ... alone)
+                double Fn[9], cost2;
+                int n2;
+                vp_refit(w, mask, n_inl, red, Rs, sFn, Fn);
+                vp_mask(w, Fn, thr2, trial, n2, cost2, red);
+                // the refitted state replaces the current one only if it is not worse
+                if (!(n2 > n_inl || (n2 == n_inl && cost2 <= cost))) break;
+                int changed = 0;
+                for (int i = tid; i < n; i += VP_RT) {
+                    changed |= mask[i] != trial[i];
+                    mask[i] = trial[i];
+                }
+                changed = __syncthreads_or(changed);
+#pragma unroll
+                for (int j = 0; j < 9; ++j) F[j] = Fn[j];
+                n_inl = n2;
+                cost = cost2;
+                if (!changed) {
+                    info = 1;
+                    break;
+                }
+            }
+        }
+    }
+    if (tid == 0) {
+        for (int j = 0; j < 9; ++j) F_out[9 * p + j] = F[j];
+        cost_out[p] = cost;
+        n_inl_out[p] = n_inl;
+        hyp_out[p] = (int32_t)bh;
+        count_out[p] = bh < 0 ? 0 : bc;
+        info_out[p] = info;
+    }
+}
+
+}  // namespace sfm
+
+using namespace sfm;
+
+extern "C" int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const double *x1, const double *x2,
+                                int64_t n_corr, const int32_t *samples, int64_t H, double threshold,
+                                int32_t min_inliers, int32_t refit_rounds, double *F, double *cost,
+                                int32_t *n_inliers, int32_t *best_hyp, int32_t *best_count, int32_t *info,
+                                uint8_t *inlier, int32_t *counts, double *models, int device) {
+    SFM_CHECK_ARG(P >= 0 && n_corr >= 0, "P < 0 or n_corr < 0");
+    SFM_CHECK_ARG(H >= 1 && H <= (int64_t)1 << 20, "H must lie in [1, 2^20]");
+    SFM_CHECK_ARG(std::isfinite(threshold) && threshold > 0.0, "threshold must be finite and positive");
+    SFM_CHECK_ARG(min_inliers >= 8, "min_inliers must be at least 8");
+    SFM_CHECK_ARG(refit_rounds >= 0, "refit_rounds < 0");
+    SFM_CHECK_ARG(P < (int64_t)0x7fffffff / H, "P x H too large for one call");
+    SFM_CHECK_ARG(pair_start, "null pointer");
+    SFM_TRY(check_csr(pair_start, P, n_corr, "pair_start", "correspondence", 0x7fffffff,
+                      "a pair has too many correspondences"));
+    int64_t n_live = 0;
+    for (int64_t p = 0; p < P; ++p) n_live += pair_start[p + 1] - pair_start[p] >= 8;
+    SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
+    SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t n = pair_start[p + 1] - pair_start[p];
+        if (n < 8) continue;
+        const int32_t *sp = samples + p * H * 8;
+        for (int64_t h = 0; h < H; ++h) {
+            const int32_t *s = sp + h * 8;
+            for (int a = 0; a < 8; ++a) {
+                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_p)");
+                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
+            }
+        }
+    }
+    if (P == 0) return 0;
+    SFM_CHECK_ARG(F && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
+                  "null pointer");
+    // info -1: fewer than eight correspondences
+    for (int64_t p = 0; p < P; ++p) {
+        if (pair_start[p + 1] - pair_start[p] >= 8) continue;
+        for (int j = 0; j < 9; ++j) F[9 * p + j] = 0.0;
+        cost[p] = 0.0;
+        n_inliers[p] = 0;
+        best_hyp[p] = -1;
+        best_count[p] = 0;
+        info[p] = -1;
+        for (int64_t k = pair_start[p]; k < pair_start[p + 1]; ++k) inlier[k] = 0;
+        if (counts) std::memset(counts + p * H, 0, (size_t)H * sizeof(int32_t));
+        if (models) std::memset(models + p * H * 9, 0, (size_t)H * 9 * sizeof(double));
+    }
+    if (n_live == 0) return 0;
+
+    ThreadCtx *c = thread_ctx(device);
+    if (!c) return SFM_ERR_HIP;
+    int rc;
+    // block table: a pair of many correspondences gets fewer hypotheses per
+    // block, so that its score loop is spread over more of them
+    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
+    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
+    int64_t blocks = 0, j = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t n = pair_start[p + 1] - pair_start[p];
+        if (n < 8) continue;
+        const int32_t ht = n >= 4 * VP_TILE ? VP_HT / 4 : (n >= VP_TILE ? VP_HT / 2 : VP_HT);
+        blk[j] = (int32_t)blocks;
+        tab[2 * j] = (int32_t)p;
+        tab[2 * j + 1] = ht;
+        blocks += (H + ht - 1) / ht;
+        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
+        ++j;
+    }
+    blk[n_live] = (int32_t)blocks;
+
+    const size_t PH = (size_t)P * (size_t)H;
+    Pack in(c->buf[0]), out(c->buf[1]);
+    const auto i_ps = in.add<int64_t>(P + 1);
+    const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
+    const auto i_s = in.add<int32_t>(8 * PH);
+    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto o_F = out.add<double>(9 * P), o_cost = out.add<double>(P);
+    const auto o_info = out.add<int32_t>(P), o_ninl = out.add<int32_t>(P);
+    const auto o_hyp = out.add<int32_t>(P), o_bc = out.add<int32_t>(P), o_cnt = out.add<int32_t>(PH);
+    const auto o_m = out.add<double>(9 * PH);
+    const auto o_mask = out.add<uint8_t>(n_corr), o_m2 = out.add<uint8_t>(n_corr);  // o_m2: the refits' trial mask
+    SFM_TRY(in.reserve());
+    SFM_TRY(out.reserve());
+    hipStream_t s = c->stream;
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(in.upload(i_ps, pair_start, s));
+    SFM_TRY(in.upload(i_x1, x1, s));
+    SFM_TRY(in.upload(i_x2, x2, s));
+    SFM_TRY(in.upload(i_s, samples, s));
+    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(tm.mark(s));
+    hipLaunchKernelGGL(k_vp_fit_score, dim3((unsigned)blocks), dim3(VP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
+                       in.ptr(i_x2), in.ptr(i_s), (int32_t)H, in.ptr(i_t), in.ptr(i_t, n_live + 1), (int32_t)n_live,
+                       threshold, out.ptr(o_m), out.ptr(o_cnt));
+    SFM_HIP(hipGetLastError());
+    SFM_TRY(tm.split(s));  // [3]: the fit-and-score kernel alone
+    hipLaunchKernelGGL(k_vp_refit, dim3((unsigned)P), dim3(VP_RT), 0, s, in.ptr(i_ps), in.ptr(i_x1), in.ptr(i_x2),
+                       (int32_t)H, threshold, min_inliers, refit_rounds, out.ptr(o_m), out.ptr(o_cnt), out.ptr(o_m2),
+                       out.ptr(o_F), out.ptr(o_cost), out.ptr(o_ninl), out.ptr(o_hyp), out.ptr(o_bc),
+                       out.ptr(o_info), out.ptr(o_mask));
+    SFM_HIP(hipGetLastError());
+    SFM_TRY(tm.mark(s));
+    // live pairs are copied out one run of consecutive pairs at a time, so that
+    // what the host wrote for the pairs of info -1 stays
+    for (int64_t p0 = 0; p0 < P;) {
+        if (pair_start[p0 + 1] - pair_start[p0] < 8) {
+            ++p0;
+            continue;
+        }
+        int64_t p1 = p0;
+        while (p1 < P && pair_start[p1 + 1] - pair_start[p1] >= 8) ++p1;
+        const size_t np = (size_t)(p1 - p0);
+        SFM_TRY(out.download(F + 9 * p0, o_F, 9 * p0, 9 * np, s));
+        SFM_TRY(out.download(cost + p0, o_cost, p0, np, s));
+        SFM_TRY(out.download(info + p0, o_info, p0, np, s));
+        SFM_TRY(out.download(n_inliers + p0, o_ninl, p0, np, s));
+        SFM_TRY(out.download(best_hyp + p0, o_hyp, p0, np, s));
+        SFM_TRY(out.download(best_count + p0, o_bc, p0, np, s));
+        const int64_t k0 = pair_start[p0], k1 = pair_start[p1];
+        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
+        if (counts) SFM_TRY(out.download(counts + p0 * H, o_cnt, p0 * H, np * H, s));
+        if (models) SFM_TRY(out.download(models + p0 * H * 9, o_m, p0 * H * 9, np * H * 9, s));
+        p0 = p1;
+    }
+    return tm.finish(s);
+}

@@ -122,6 +122,53 @@ class MatchStore:
         xy = np.column_stack([self.x[index], self.y[index]])
         return view_start.astype(np.int64), pt_idx, xy, index
 
+    def pairs(self, images=None, min_matches=8, use_flags=False):
+        """The image pairs of pair verification: for every pair (i, j) of
+        ``images`` (distinct image numbers, default all of them) in
+        itertools.combinations order that has at least ``min_matches``
+        features observed in both (flagged in both with ``use_flags``), its
+        correspondences -- what np.where(flag[:, i] & flag[:, j]) selects on
+        the dense matrices (Wrapper_dev.py:73-80), built from the COO rows
+        alone.  Returns (pair_ij (P, 2) image numbers, pair_start (P + 1,)
+        int64, index1, index2): pair p owns [pair_start[p], pair_start[p + 1])
+        of index1 / index2, the store indices of the correspondence's
+        observation in pair_ij[p, 0] and in pair_ij[p, 1], features ascending
+        within a pair."""
+        images = np.arange(self.n_images) if images is None else np.asarray(images, dtype=np.int64).reshape(-1)
+        n = len(images)
+        if n and (images.min() < 0 or images.max() >= self.n_images or len(np.unique(images)) != n):
+            raise ValueError("pairs: images must be distinct and in [0, n_images)")
+        pos = np.full(self.n_images, -1, dtype=np.int64)
+        pos[images] = np.arange(n)
+        keep = pos[self.image] >= 0
+        if use_flags:
+            keep &= self.flag == 1
+        kept = np.where(keep)[0]
+        # kept observations per feature row, from the rows' extents
+        before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+        lo, m = before[self._row_start[:-1]], np.diff(before[self._row_start])
+        o1, o2 = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+        for k in np.unique(m[m >= 2]):  # rows have few observations: vectorise per length
+            first = lo[m == k]
+            for a in range(int(k) - 1):
+                for b in range(a + 1, int(k)):
+                    o1.append(kept[first + a])
+                    o2.append(kept[first + b])
+        o1, o2 = np.concatenate(o1), np.concatenate(o2)
+        swap = pos[self.image[o1]] > pos[self.image[o2]]  # the first observation is the earlier of `images`
+        o1, o2 = np.where(swap, o2, o1), np.where(swap, o1, o2)
+        a, b = pos[self.image[o1]], pos[self.image[o2]]
+        pid = a * n - a * (a + 1) // 2 + (b - a - 1)  # the pair's place among the combinations
+        per_pair = np.bincount(pid, minlength=n * (n - 1) // 2)
+        live = per_pair >= max(int(min_matches), 1)
+        sel = live[pid]
+        o1, o2, pid = o1[sel], o2[sel], pid[sel]
+        order = np.lexsort((self.feature[o1], pid))
+        ia, ib = np.triu_indices(n, 1)
+        pair_ij = np.column_stack([images[ia[live]], images[ib[live]]]).astype(np.int64).reshape(-1, 2)
+        pair_start = np.concatenate([[0], np.cumsum(per_pair[live], dtype=np.int64)]).astype(np.int64)
+        return pair_ij, pair_start, o1[order], o2[order]
+
     def observations(self, filtered_world_coords, n_cameras, use_flags=True):
         """COO inputs of bundle adjustment in the reference's order
         (BundleAdjustment.py:164-169): valid points ascending, cameras

@@ -13,6 +13,10 @@ tracks built from pairwise matches hold wrong observations, and the bundle
 adjuster has no robust loss.  It fits every track to the observations that
 agree (``sfm_triangulate_tracks_robust``), says which tracks to keep and can
 clear the store's flags of everything else.
+
+``verify_pairs`` is the stage before all of them: F-RANSAC for every image pair
+of the store in one call (``sfm_verify_pairs``), which sets the flags the others
+read.
 """
 import numpy as np
 
@@ -86,6 +90,37 @@ def register_views(store, K, feature_rows, X, candidates, H=256, seed=0, thresho
         registered = np.repeat(out[7] >= 1, np.diff(view_start))
         store.flag[index[registered & ~out[4]]] = 0
     return order, out, index
+
+
+def verify_pairs(store, images=None, H=256, seed=0, threshold=2.5, min_inliers=8, min_matches=8,
+                 update_flags=False):
+    """The first stage of the pipeline: the epipolar geometry of every image
+    pair of ``store`` over ``images`` (default all) in one device call
+    (``_sfmcore.verify_pairs``: 8-point F-RANSAC over H hypotheses per pair
+    under x2^T F x1 = 0, the Sampson distance as the inlier rule, a
+    least-squares refit on the consensus set, one inlier mask per
+    correspondence).  It replaces the reference's pair loop
+    (Wrapper_dev.py:69-123), whose F does not fit its own sample points.
+    Returns (order, pair_ij, out, index1, index2): ``pair_ij`` (P, 2) and the
+    store indices ``index1`` / ``index2`` of every correspondence's two
+    observations are ``store.pairs(images, min_matches)``'s, ``out`` is
+    ``_sfmcore.verify_pairs``'s tuple (F, cost, n_inliers, inlier, best_hyp,
+    best_count, info) over them, ``order`` the pairs by decreasing n_inliers
+    (stable), so pair_ij[order[0]] is the candidate initial pair.  With
+    ``update_flags`` the store's flag is set to 1 for both observations of
+    every inlier correspondence of every pair with info >= 0 -- what
+    Wrapper_dev.py:122-123 does to filtered_feature_flags; no flag is cleared."""
+    pair_ij, pair_start, index1, index2 = store.pairs(images, min_matches=min_matches)
+    x1 = np.column_stack([store.x[index1], store.y[index1]])
+    x2 = np.column_stack([store.x[index2], store.y[index2]])
+    samples = _core.pair_samples(np.diff(pair_start), H, seed)
+    out = _core.verify_pairs(pair_start, x1, x2, samples, threshold=threshold, min_inliers=min_inliers)
+    order = np.argsort(-out[2].astype(np.int64), kind="stable")
+    if update_flags:
+        ok = np.repeat(out[6] >= 0, np.diff(pair_start)) & out[3]
+        store.flag[index1[ok]] = 1
+        store.flag[index2[ok]] = 1
+    return order, pair_ij, out, index1, index2
 
 
 def robust_keep(out, min_inliers, min_angle_deg):
