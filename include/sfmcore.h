@@ -461,7 +461,12 @@ typedef struct {
 
 /* Observations must be point-major (sorted by pt_idx, as the reference
  * assembles them: BundleAdjustment.py:164-169).  cam_params (n_cams x 6)
- * and points (n_pts x 3) are updated in place. */
+ * and points (n_pts x 3) are updated in place.
+ * SFM_ERR_ARG, with nothing touched: a camera or point index out of range,
+ * observations not point-major, a point observed twice by the same camera,
+ * more than 682 cameras, and an empty problem (n_pts == 0 or n_obs == 0:
+ * nothing to adjust).  Points and cameras without observations are allowed
+ * and do not move.  Within a communicator a rank's shard may be empty. */
 int sfm_ba_lm(int32_t n_cams, int64_t n_pts, int64_t n_obs, const int32_t *cam_idx,
               const int32_t *pt_idx, const double *obs, const double *K, double *cam_params,
               double *points, const sfm_ba_opts *opts, sfm_ba_report *report, int device);

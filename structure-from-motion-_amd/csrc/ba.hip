@@ -4069,6 +4069,8 @@ static int ba_create(int32_t nc, int64_t np_, int64_t no, const int32_t *cam, co
                      sfm_ba_problem **out, bool oneshot = false) {
     SFM_CHECK_ARG(out && K && cams && (pts || np_ == 0) && (no == 0 || dense || (cam && pt && obs)), "null pointer");
     SFM_CHECK_ARG(nc >= 1 && np_ >= 0 && no >= 0, "bad sizes");
+    // an empty problem is an argument error; a rank of a communicator may hold an empty shard
+    SFM_CHECK_ARG(comm || (np_ >= 1 && no >= 1), "no points or no observations (nothing to adjust)");
     SFM_CHECK_ARG(no < ((int64_t)1 << 31), "problem too large for int32 indexing");
     SFM_CHECK_ARG(6 * nc <= SOLVE_MAX, "at most 682 cameras (dense reduced camera system)");
     // SFM_CREATE_TIMING=1: the host phases of create on stderr (measurement)
@@ -5243,7 +5245,14 @@ extern "C" int sfm_ba_download(sfm_ba_problem *p, double *cams, double *pts) {
     SFM_HIP(hipStreamSynchronize(p->stream));
     if (cams)
         for (int c = 0; c < p->nc; ++c) {
-            h_R_to_rotvec(&Rt[12 * c], cams + 6 * c);
+            // a rotation no step has touched (every step rejected, a camera
+            // without observations) goes back as the rotation vector it came as
+            double R0[9];
+            h_rotvec_to_R(&p->cams0[6 * c], R0);
+            if (!std::memcmp(R0, &Rt[12 * c], sizeof R0))
+                std::memcpy(cams + 6 * c, &p->cams0[6 * c], 3 * sizeof(double));
+            else
+                h_R_to_rotvec(&Rt[12 * c], cams + 6 * c);
             for (int i = 0; i < 3; ++i) cams[6 * c + 3 + i] = Rt[12 * c + 9 + i];
         }
     return 0;
