@@ -423,6 +423,74 @@ int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const double *x1, con
                      int device);
 
 /* ---------------------------------------------------------------------
+ * Batched initial-pair selection: for every verified pair in one call, the
+ * relative pose from its F, the cheirality counts of the four candidates, the
+ * winner's points with their parallax angles and the support of the best
+ * 4-point homography -- what tells a wide-baseline pair from one without
+ * baseline or of a plane (the pair of most inliers is usually the former's
+ * opposite).  The reference starts from its first two images and has no
+ * counterpart; sfm_two_view_select serves one pair from host-built candidates.
+ * K 3 x 3.  The P pairs are CSR rows as for sfm_verify_pairs: pair_start (P +
+ * 1), x1 and x2 (n_corr x 2); every row given is used, so the caller passes the
+ * verified inliers only.  F (P x 9, row-major) under x2^T F x1 = 0, as
+ * sfm_verify_pairs returns it.  hsamples (P x Hh x 4): each entry a position
+ * inside its pair, in [0, n_p), the four of a hypothesis distinct; ignored for
+ * pairs of n_p < 4; null exactly when Hh = 0.  h_threshold and max_reproj are
+ * in pixels, finite and > 0; 0 <= Hh <= 2^20.  A violation is SFM_ERR_ARG,
+ * found on the host before anything is launched.
+ * Per pair, on the device in fp64:
+ * Candidates: E = K^T F K = U diag(s) V^T by one-sided Jacobi; with W = [[0, -1,
+ * 0], [1, 0, 0], [0, 0, 1]], R_a = U W V^T and R_b = U W^T V^T, each negated
+ * where its determinant is negative; t = u3, the left singular vector of the
+ * least singular value; the candidates are (R_a, t), (R_a, -t), (R_b, t), (R_b,
+ * -t).  Camera 1 is K [I | 0], camera 2 K [R | t] with centre C = -R^T t, |C| =
+ * 1.  Which place a candidate takes among the four follows the signs the
+ * decomposition happens to return: only the set is specified.
+ * Cheirality: every correspondence is triangulated under every candidate as
+ * sfm_triangulate_dlt does and counts for it under sfm_two_view_select's rule
+ * (in front of both cameras); counts (P x 4); best: the first candidate with
+ * the strictly largest count.
+ * Under the winner, per correspondence: X (n_corr x 3); good (n_corr), 1 where X
+ * is finite, lies in front of both cameras and its squared reprojection error
+ * is < max_reproj^2 in each image; angle (n_corr) = atan2(|a x b|, a.b) in
+ * radians with a = X and b = X - C, 0 where not good (and where the expression
+ * is not a number).  Per pair: R (P x 9) and C (P x 3) of the winner; n_good;
+ * median_angle, the lower median of the good angles -- the element of sorted
+ * index (n_good - 1) / 2, one of the pair's own angle values bit for bit (an
+ * exact selection, no histogram estimate), 0 with none.
+ * Homography support (Hh > 0): a hypothesis is the normalised 4-point DLT under
+ * x2 ~ H x1 -- Hartley normalisation of the four points on each side, the rows
+ * [0, 0, 0, -a, -b, -1, d a, d b, d] and [a, b, 1, 0, 0, 0, -c a, -c b, -c] with
+ * (a, b) the normalised first point and (c, d) the second, the null vector of
+ * the 8 x 9 system, H = T2^-1 H^ T1, scaled to unit Frobenius norm with the sign
+ * that makes the entry of largest magnitude (the first such in row-major order)
+ * positive; no division by H[2,2] (not find_homography's convention; differs on
+ * purpose).  A correspondence is an inlier where, with h = H [x1; 1], h2 is
+ * finite, |h2| >= 1e-12 and (u2 - h0/h2)^2 + (v2 - h1/h2)^2 < h_threshold^2.
+ * The winner has the most inliers, then the earliest place in the table.
+ * h_count, h_best (-1 without one: Hh = 0, or no hypothesis with an inlier),
+ * Hbest (P x 9, zeros without a winner).
+ * info (P): 0 done; -1 n_p < 8 (nothing of the pair is read on or from the
+ * device, the homography stage included: R = I, C = 0, counts 0, best 0, X 0,
+ * nothing good, angles 0, h_count 0, h_best -1, Hbest 0); -2 F or E is not
+ * finite or the second singular value of E is 0 (the outputs of -1, but the
+ * homography stage runs).
+ * Nullable: cands (P x 4 x 12: R row-major, then t), hcounts (P x Hh), hmodels
+ * (P x Hh x 9); zero for pairs that are not processed (cands: info < 0, the
+ * other two: info -1).
+ * Counts are integers and every other value comes from the pair alone: a pair's
+ * outputs are the same bits alone, in any batch and at any place in it.  Two
+ * launches (one with Hh = 0) and one synchronisation whatever P is; P == 0, or
+ * no pair of eight correspondences, returns without touching a device.
+ * sfm_last_timings: upload, both kernels, download, the homography kernel alone.
+ * ------------------------------------------------------------------- */
+int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_t P, const double *x1, const double *x2,
+                   int64_t n_corr, const double *F, const int32_t *hsamples, int64_t Hh, double h_threshold,
+                   double max_reproj, double *R, double *C, int64_t *counts, int32_t *best, int32_t *n_good,
+                   double *median_angle, int32_t *h_count, int32_t *h_best, double *Hbest, int32_t *info, double *X,
+                   uint8_t *good, double *angle, double *cands, int32_t *hcounts, double *hmodels, int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

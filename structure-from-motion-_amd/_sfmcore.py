@@ -107,6 +107,8 @@ SIGNATURES = [
                                 _c]),
     ("sfm_verify_pairs", _c, [_i64, _i, _d, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _d,
                               _d, _i32, _i32, _i32, _i32, _u8, _i32, _d, _c]),
+    ("sfm_init_pairs", _c, [_d, _i64, _i, _d, _d, _i, _d, _i32, _i, ctypes.c_double, ctypes.c_double, _d, _d, _i64,
+                            _i32, _i32, _d, _i32, _i32, _d, _i32, _d, _u8, _d, _d, _i32, _d, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -912,6 +914,92 @@ def verify_pairs(pair_start, x1, x2, samples, threshold=2.5, min_inliers=8, refi
         out += (counts,)
     if want_models:
         out += (models.reshape(P, H, 3, 3),)
+    return out
+
+
+def homography_samples(counts, H, seed):
+    """The 4-point sample table of init_pairs for pairs of ``counts``
+    correspondences: (P, H, 4) int32, drawn as pair_samples draws -- pair p from
+    child p of numpy.random.default_rng(seed), the rows that hold a duplicate
+    redrawn until none do, so a pair's table does not depend on the other
+    pairs; a pair of n_p < 4 gets zeros."""
+    return _sample_tables(counts, H, seed, 4, "homography_samples")
+
+
+def init_pairs(K, pair_start, x1, x2, F, hsamples=None, h_threshold=4.0, max_reproj=4.0, want_cands=False,
+               want_hcounts=False, want_hmodels=False):
+    """Batched initial-pair selection (sfm_init_pairs): for every pair, the
+    four pose candidates of E = K^T F K, their cheirality counts over the
+    pair's correspondences, the winner's pose and points with their parallax
+    angles and, with ``hsamples`` (P, Hh, 4; homography_samples), the inlier
+    count of the best 4-point homography.  The pairs are CSR rows: pair p owns
+    x1 / x2[pair_start[p]:pair_start[p + 1]], every row is used (pass the
+    verified inliers); F (P, 3, 3) under x2^T F x1 = 0, as verify_pairs
+    returns it.
+    Returns (R (P, 3, 3), C (P, 3), counts (P, 4) int64, best (P,) int32, n_good
+    (P,) int32, median_angle (P,) the lower median of the good angles in
+    radians, h_count (P,) int32, h_best (P,) int32 (-1 without one), Hbest (P,
+    3, 3), info (P,) int32: 0 done, -1 fewer than eight correspondences, -2 F or
+    E not finite or of rank below 2; X (n_corr, 3), good (n_corr,) bool, angle
+    (n_corr,)), then cands (P, 4, 12: R row-major, then t) with want_cands,
+    hcounts (P, Hh) int32 with want_hcounts and hmodels (P, Hh, 3, 3) with
+    want_hmodels.  The arguments are checked before a device is looked for;
+    P = 0, or no pair of eight correspondences, returns without one."""
+    K = _f64(K)
+    ps = np.ascontiguousarray(pair_start, dtype=np.int64).reshape(-1)
+    x1 = _f64(x1).reshape(-1, 2)
+    x2 = _f64(x2).reshape(-1, 2)
+    F = _f64(F)
+    if K.size != 9:
+        raise ValueError("init_pairs: K must be 3 x 3")
+    if len(ps) < 1 or len(x1) != len(x2):
+        raise ValueError("init_pairs: pair_start needs P + 1 entries and x1, x2 one row per correspondence")
+    P = len(ps) - 1
+    if F.size != 9 * P:
+        raise ValueError("init_pairs: F must be (P, 3, 3)")
+    F = F.reshape(P, 9)
+    Hh = 0
+    if hsamples is not None:
+        hsamples = np.ascontiguousarray(hsamples, dtype=np.int32)
+        if hsamples.ndim != 3 or hsamples.shape[0] != P or hsamples.shape[2] != 4:
+            raise ValueError("init_pairs: hsamples must be (P, Hh, 4)")
+        Hh = hsamples.shape[1]
+        if Hh == 0:
+            hsamples = None
+    h_threshold, max_reproj = float(h_threshold), float(max_reproj)
+    bad = (not (np.isfinite(h_threshold) and h_threshold > 0) or not (np.isfinite(max_reproj) and max_reproj > 0)
+           or Hh > 1 << 20 or ps[0] != 0 or bool(np.any(np.diff(ps) < 0)) or ps[-1] != len(x1))
+    if not bad:
+        n_p = np.diff(ps)
+        sampled = n_p >= 4
+        if Hh and sampled.any():
+            s = hsamples[sampled]
+            srt = np.sort(s, axis=2)
+            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_p[sampled]).any()
+                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
+        if not bad and (n_p >= 8).any():
+            require_device()
+    R, C, med, Hbest = np.zeros((P, 9)), np.zeros((P, 3)), np.zeros(P), np.zeros((P, 9))
+    counts = np.zeros((P, 4), dtype=np.int64)
+    best, n_good, h_count, h_best, info = (np.zeros(P, dtype=np.int32) for _ in range(5))
+    X, good, angle = np.zeros((len(x1), 3)), np.zeros(len(x1), dtype=np.uint8), np.zeros(len(x1))
+    cands = np.zeros((P, 4, 12)) if want_cands else None
+    hcounts = np.zeros((P, Hh), dtype=np.int32) if want_hcounts else None
+    hmodels = np.zeros((P, Hh, 9)) if want_hmodels else None
+    _check(_lib.sfm_init_pairs(
+        _p(K), _p(ps, _i64), P, _p(x1), _p(x2), len(x1), _p(F), _p(hsamples, _i32) if Hh else None, Hh, h_threshold,
+        max_reproj, _p(R), _p(C), _p(counts, _i64), _p(best, _i32), _p(n_good, _i32), _p(med), _p(h_count, _i32),
+        _p(h_best, _i32), _p(Hbest), _p(info, _i32), _p(X), _p(good, _u8), _p(angle),
+        _p(cands) if want_cands else None, _p(hcounts, _i32) if want_hcounts else None,
+        _p(hmodels) if want_hmodels else None, DEVICE))
+    out = (R.reshape(P, 3, 3), C, counts, best, n_good, med, h_count, h_best, Hbest.reshape(P, 3, 3), info, X,
+           good.astype(bool), angle)
+    if want_cands:
+        out += (cands,)
+    if want_hcounts:
+        out += (hcounts,)
+    if want_hmodels:
+        out += (hmodels.reshape(P, Hh, 3, 3),)
     return out
 
 

@@ -16,7 +16,9 @@ clear the store's flags of everything else.
 
 ``verify_pairs`` is the stage before all of them: F-RANSAC for every image pair
 of the store in one call (``sfm_verify_pairs``), which sets the flags the others
-read.
+read.  ``init_pairs`` follows it: the pose, cheirality, parallax and
+homography support of every verified pair in one call (``sfm_init_pairs``), and
+from them the pair to start the reconstruction from.
 """
 import numpy as np
 
@@ -121,6 +123,79 @@ def verify_pairs(store, images=None, H=256, seed=0, threshold=2.5, min_inliers=8
         store.flag[index1[ok]] = 1
         store.flag[index2[ok]] = 1
     return order, pair_ij, out, index1, index2
+
+
+def init_pairs(store, K, verified, Hh=128, seed=0, h_threshold=4.0, max_reproj=4.0, min_points=30, min_angle_deg=4.0,
+               max_h_ratio=0.8):
+    """Which pair to start the reconstruction from, and with what pose and
+    points: every verified pair in one device call (``_sfmcore.init_pairs``:
+    the pose candidates of its F, cheirality, the winner's points, their
+    parallax angles and the support of the best of Hh 4-point homographies).
+    The pair of most inliers, ``verify_pairs``'s order[0], is usually the one of
+    least baseline, or of a plane: its translation and points are noise.
+    ``verified`` is the tuple ``verify_pairs`` returned.  Every pair with verify
+    info >= 0 is compacted to its inlier correspondences; the others become
+    empty rows.
+    Returns (order, eligible, out, pair_start, index1, index2): ``out`` is
+    ``_sfmcore.init_pairs``'s tuple over the compacted CSR rows ``pair_start``,
+    ``index1`` / ``index2`` the store indices of their observations;
+    ``eligible`` (P,) marks the pairs with info == 0, n_good >= min_points,
+    median_angle >= min_angle_deg and h_count <= max_h_ratio n_p; ``order``
+    puts the eligible pairs first by decreasing n_good (stable), then the rest
+    by decreasing n_good.  So pair_ij[order[0]] with out's R, C and the X rows
+    where good, together with store.feature[index1], seeds triangulate_store /
+    register_views.  The three thresholds are policy defaults to override, not
+    measured quantities."""
+    _, pair_ij, vout, i1, i2 = verified
+    F, inlier, vinfo = vout[0], np.asarray(vout[3], dtype=bool), vout[6]
+    P = len(pair_ij)
+    n_all = len(i1)
+    # the pair of every correspondence: verify_pairs' rows are store.pairs' rows
+    if P:
+        bounds = _pair_bounds(store, verified)
+        per = np.repeat(np.arange(P), np.diff(bounds))
+    else:
+        per = np.zeros(0, dtype=np.int64)
+    keep = inlier & (np.asarray(vinfo)[per] >= 0) if n_all else np.zeros(0, dtype=bool)
+    n_p = np.bincount(per[keep], minlength=P).astype(np.int64)
+    pair_start = np.concatenate([[0], np.cumsum(n_p)]).astype(np.int64)
+    index1, index2 = np.asarray(i1)[keep], np.asarray(i2)[keep]
+    x1 = np.column_stack([store.x[index1], store.y[index1]])
+    x2 = np.column_stack([store.x[index2], store.y[index2]])
+    hs = _core.homography_samples(n_p, Hh, seed) if Hh else None
+    out = _core.init_pairs(K, pair_start, x1, x2, F, hs, h_threshold=h_threshold, max_reproj=max_reproj)
+    order, eligible = rank_initial_pairs(out, n_p, min_points, min_angle_deg, max_h_ratio)
+    return order, eligible, out, pair_start, index1, index2
+
+
+def _pair_bounds(store, verified):
+    """the CSR row starts of verify_pairs' correspondences: rows are runs of equal
+    (image1, image2) in store.pairs' order, so they follow from the images"""
+    _, pair_ij, _, i1, i2 = verified
+    key = store.image[np.asarray(i1)].astype(np.int64) * store.n_images + store.image[np.asarray(i2)]
+    want = np.asarray(pair_ij, dtype=np.int64).reshape(-1, 2)
+    want = want[:, 0] * store.n_images + want[:, 1]
+    # every pair has a correspondence and no two pairs share their images
+    starts = np.concatenate([[0], np.flatnonzero(np.diff(key)) + 1, [len(key)]]).astype(np.int64)
+    if len(starts) != len(want) + 1 or not np.array_equal(key[starts[:-1]], want):
+        raise ValueError("init_pairs: `verified` does not belong to this store")
+    return starts
+
+
+def rank_initial_pairs(out, n_p, min_points=30, min_angle_deg=4.0, max_h_ratio=0.8):
+    """(order, eligible) of init_pairs' outputs ``out`` over pairs of ``n_p``
+    correspondences: eligible where info == 0, n_good >= min_points,
+    median_angle >= min_angle_deg and h_count <= max_h_ratio n_p; order puts the
+    eligible pairs first by decreasing n_good (stable), then the rest by
+    decreasing n_good."""
+    n_good, median, h_count, info = out[4], out[5], out[6], out[9]
+    n_p = np.asarray(n_p, dtype=np.int64)
+    eligible = ((np.asarray(info) == 0) & (np.asarray(n_good) >= min_points)
+                & (np.asarray(median) >= np.deg2rad(min_angle_deg))
+                & (np.asarray(h_count) <= max_h_ratio * n_p))
+    ng = np.asarray(n_good, dtype=np.int64)
+    order = np.lexsort((np.arange(len(ng)), -ng, ~eligible))
+    return order, eligible
 
 
 def robust_keep(out, min_inliers, min_angle_deg):
