@@ -423,6 +423,80 @@ int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const double *x1, con
                      int device);
 
 /* ---------------------------------------------------------------------
+ * Batched calibrated pair verification: 5-point essential-matrix RANSAC and a
+ * five-parameter refit for every image pair in one call, under
+ * sfm_verify_pairs' convention (x2^T F x1 = 0, unit-norm models, the Sampson
+ * distance in pixels).  The reference has no counterpart.  Unlike the 8-point F
+ * the model exists for a pair that sees one plane.  Pure rotation (t = 0, E
+ * undefined) is out of scope.
+ * K 3 x 3, finite, with a non-zero determinant; K^-1 is formed once on the host
+ * by the adjugate.  The P pairs are CSR rows exactly as for sfm_verify_pairs:
+ * pair_start (P + 1), x1 and x2 (n_corr x 2).  samples (P x H x 5): each entry a
+ * position inside its pair, in [0, n_p), the five of a hypothesis distinct;
+ * ignored for pairs of n_p < 5.  threshold is in pixels, finite and > 0; 1 <= H
+ * <= 2^20; min_inliers >= 5; refit_rounds >= 0; max_nfev > 0.  A violation is
+ * SFM_ERR_ARG, found on the host before anything is launched, with no output
+ * touched.
+ * Hypothesis: with x^ = K^-1 [x; 1] (dehomogenised), the 5 x 9 system of design
+ * rows [c a, c b, c, d a, d b, d, a, b, 1], (a, b) = x^1 and (c, d) = x^2, so that
+ * x^2^T E x^1 = 0 for E row-major; an orthonormal basis X, Y, Z, W of its
+ * four-dimensional null space (Householder); every E = x X + y Y + z Z + W with
+ * det E = 0 and 2 E E^T E - tr(E E^T) E = 0.  These ten cubics over the 20
+ * monomials are reduced by Gauss-Jordan with partial pivoting on the ten
+ * columns that hold x or y to a power of two or more, which leaves B(z) [x, y,
+ * 1]^T = 0 with a 3 x 3 polynomial matrix; the roots of det B, of degree 10,
+ * are found by Aberth iteration from fixed starting points (at most 64 sweeps),
+ * a root counts as real where |Im z| <= 1e-8 max(1, |Re z|) and is polished by
+ * three Newton steps; x and y follow from the null vector of B(z).  Each
+ * solution is scaled to unit Frobenius norm with the sign that makes the entry
+ * of largest magnitude (the first such in row-major order) positive; solutions
+ * that are not finite are dropped.  There are up to ten per hypothesis: n_sol
+ * counts them, and only their set is specified, not their order.
+ * Score: F = K^-T E K^-1 brought to unit norm and sign in the same way, then
+ * sfm_verify_pairs' inlier rule, e e < threshold^2 den with den > 0 (the fp64
+ * expression decides).  The winner over all (hypothesis, solution) pairs has
+ * the most inliers, then the smaller sum of the inliers' squared Sampson
+ * distances, then the earlier hypothesis (then the earlier solution).
+ * Refit: E = +-s [t]x R by one-sided Jacobi (R = U W V^T, negated where its
+ * determinant is negative; t = u3), then Levenberg-Marquardt on five
+ * parameters -- a rotation increment multiplied from the left, and t moved in
+ * the tangent plane of the unit sphere spanned by b1 = t x e_k / |t x e_k| (k
+ * the axis of the smallest |t_k|, the first of equals) and b2 = t x b1, then
+ * renormalised -- over the current inliers' Sampson distances e / sqrt(den) in
+ * pixels, controlled as sfm_register_views' refit: lambda 1e-3, / 10 on an
+ * accepted and x 10 on a rejected step, only steps that lower the cost
+ * accepted, MINPACK's stop tests at 1e-8 and at most max_nfev cost evaluations.
+ * Every correspondence of the pair is then scored against the refitted E, and
+ * (count, then smaller cost) replaces the current state only if it is not
+ * worse; up to refit_rounds rounds, ending early when the mask does not
+ * change.  So n_inliers >= best_count.
+ * Outputs per pair: E (P x 9) and F (P x 9), row-major, both of unit norm, F =
+ * K^-T E K^-1 up to scale (F goes straight into sfm_init_pairs); cost (the sum
+ * of the final inliers' squared Sampson distances), n_inliers, best_hyp (-1
+ * without one), best_count, info: 1..5 the last refit's stop code (1 ftol, 2
+ * xtol, 3 both, 4 gtol, 5 max_nfev), 0 refit_rounds = 0, -1 n_p < 5 (E = F = 0,
+ * nothing an inlier; nothing of the pair is read on or from the device), -2 no
+ * finite solution in any hypothesis (the same outputs), -3 best_count <
+ * min_inliers (the winning solution's E, F, mask, count and cost, no refit), -4
+ * the refit's start had no finite cost or E no factorisation (as -3).
+ * Per correspondence: inlier (n_corr), 1 or 0.  Nullable: n_sol (P x H), counts
+ * (P x H x 10) the inliers per solution, models (P x H x 10 x 9) the solutions
+ * E; the slots past n_sol are zero, and all three are zero for a pair of n_p <
+ * 5.
+ * No sum depends on the batch and there are no float atomics: a pair's outputs
+ * are the same bits alone, in any batch and at any place in it, and a
+ * hypothesis's n_sol, counts and models do not depend on H.  Two launches and
+ * one synchronisation whatever P is; P == 0, or no pair of five
+ * correspondences, returns without touching a device.  sfm_last_timings:
+ * upload, both kernels, download, the fit-and-score kernel alone.
+ * ------------------------------------------------------------------- */
+int sfm_essential_pairs(const double *K, const int64_t *pair_start, int64_t P, const double *x1,
+                        const double *x2, int64_t n_corr, const int32_t *samples, int64_t H, double threshold,
+                        int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev, double *E, double *F,
+                        double *cost, int32_t *n_inliers, int32_t *best_hyp, int32_t *best_count, int32_t *info,
+                        uint8_t *inlier, int32_t *n_sol, int32_t *counts, double *models, int device);
+
+/* ---------------------------------------------------------------------
  * Batched initial-pair selection: for every verified pair in one call, the
  * relative pose from its F, the cheirality counts of the four candidates, the
  * winner's points with their parallax angles and the support of the best

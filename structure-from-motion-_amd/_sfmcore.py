@@ -107,6 +107,8 @@ SIGNATURES = [
                                 _c]),
     ("sfm_verify_pairs", _c, [_i64, _i, _d, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _d,
                               _d, _i32, _i32, _i32, _i32, _u8, _i32, _d, _c]),
+    ("sfm_essential_pairs", _c, [_d, _i64, _i, _d, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                 ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32, _i32, _d, _c]),
     ("sfm_init_pairs", _c, [_d, _i64, _i, _d, _d, _i, _d, _i32, _i, ctypes.c_double, ctypes.c_double, _d, _d, _i64,
                             _i32, _i32, _d, _i32, _i32, _d, _i32, _d, _u8, _d, _d, _i32, _d, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
@@ -914,6 +916,82 @@ def verify_pairs(pair_start, x1, x2, samples, threshold=2.5, min_inliers=8, refi
         out += (counts,)
     if want_models:
         out += (models.reshape(P, H, 3, 3),)
+    return out
+
+
+def essential_samples(counts, H, seed):
+    """The 5-point sample table of essential_pairs for pairs of ``counts``
+    correspondences: (P, H, 5) int32, drawn as pair_samples draws -- pair p from
+    child p of numpy.random.default_rng(seed), the rows that hold a duplicate
+    redrawn until none do, so a pair's table does not depend on the other
+    pairs; a pair of n_p < 5 gets zeros."""
+    return _sample_tables(counts, H, seed, 5, "essential_samples")
+
+
+def essential_pairs(K, pair_start, x1, x2, samples, threshold=2.5, min_inliers=5, refit_rounds=3, max_nfev=50,
+                    want_counts=False, want_models=False):
+    """Batched calibrated pair verification (sfm_essential_pairs): for every
+    image pair, 5-point essential-matrix RANSAC over the host-drawn ``samples``
+    (P, H, 5; essential_samples) -- up to ten solutions per hypothesis, each
+    scored in pixels by the Sampson distance of F = K^-T E K^-1 --, the winner
+    (most inliers, then the smaller cost, then the earliest hypothesis)
+    refitted as E = [t]x R by Levenberg-Marquardt over its consensus set in up
+    to ``refit_rounds`` rounds, and the inlier mask of the pair's
+    correspondences.  The pairs are CSR rows as for verify_pairs.
+    Returns (F (P, 3, 3) and, at position 7, E (P, 3, 3), both of unit
+    Frobenius norm, cost (P,) sum of the final inliers' squared Sampson
+    distances, n_inliers (P,) int32, inlier (n_corr,) bool, best_hyp (P,) int32,
+    best_count (P,) int32, info (P,) int32: 1..5 the last refit's stop code, 0
+    no refit asked for, -1 fewer than five correspondences, -2 no finite
+    solution, -3 best_count < min_inliers, -4 refit could not start, E), then
+    n_sol (P, H) int32 and counts (P, H, 10) int32 with want_counts and models
+    (P, H, 10, 3, 3) with want_models: positions 0-6 are verify_pairs' tuple.
+    The arguments are checked before a device is looked for; P = 0, or no pair
+    of five correspondences, returns without one."""
+    K = _f64(K)
+    ps = np.ascontiguousarray(pair_start, dtype=np.int64).reshape(-1)
+    x1 = _f64(x1).reshape(-1, 2)
+    x2 = _f64(x2).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    if K.size != 9:
+        raise ValueError("essential_pairs: K must be 3 x 3")
+    if len(ps) < 1 or len(x1) != len(x2):
+        raise ValueError("essential_pairs: pair_start needs P + 1 entries and x1, x2 one row per correspondence")
+    P = len(ps) - 1
+    if samples.ndim != 3 or samples.shape[0] != P or samples.shape[2] != 5 or samples.shape[1] < 1:
+        raise ValueError("essential_pairs: samples must be (P, H, 5) with H >= 1")
+    H = samples.shape[1]
+    threshold = float(threshold)
+    with np.errstate(all="ignore"):
+        bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 5 or int(refit_rounds) < 0
+               or int(max_nfev) <= 0 or not np.all(np.isfinite(K)) or not np.linalg.det(K.reshape(3, 3)) != 0
+               or ps[0] != 0 or bool(np.any(np.diff(ps) < 0)) or ps[-1] != len(x1))
+    if not bad:
+        n_p = np.diff(ps)
+        live = n_p >= 5
+        if live.any():
+            s = samples[live]
+            srt = np.sort(s, axis=2)
+            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_p[live]).any()
+                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
+            if not bad:
+                require_device()
+    E, F, cost = np.zeros((P, 9)), np.zeros((P, 9)), np.zeros(P)
+    n_inl, hyp, count, info = (np.zeros(P, dtype=np.int32) for _ in range(4))
+    inlier = np.zeros(len(x1), dtype=np.uint8)
+    n_sol = np.zeros((P, H), dtype=np.int32) if want_counts else None
+    counts = np.zeros((P, H, 10), dtype=np.int32) if want_counts else None
+    models = np.zeros((P, H, 10, 9)) if want_models else None
+    _check(_lib.sfm_essential_pairs(
+        _p(K), _p(ps, _i64), P, _p(x1), _p(x2), len(x1), _p(samples, _i32), H, threshold, int(min_inliers),
+        int(refit_rounds), int(max_nfev), _p(E), _p(F), _p(cost), _p(n_inl, _i32), _p(hyp, _i32), _p(count, _i32),
+        _p(info, _i32), _p(inlier, _u8), _p(n_sol, _i32) if want_counts else None,
+        _p(counts, _i32) if want_counts else None, _p(models) if want_models else None, DEVICE))
+    out = (F.reshape(P, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info, E.reshape(P, 3, 3))
+    if want_counts:
+        out += (n_sol, counts)
+    if want_models:
+        out += (models.reshape(P, H, 10, 3, 3),)
     return out
 
 

@@ -1,0 +1,502 @@
+// Batched calibrated pair verification: the essential matrix of every image
+// pair of a store in one call.  The calibrated member of the family of
+// verify_pairs.hip: every pair brings its correspondences (CSR over pairs) and a
+// host-drawn table of 5-point samples; one call returns, per pair, the RANSAC
+// winner over all (hypothesis, solution) pairs, the pose E = [t]x R refitted to
+// its consensus set by Levenberg-Marquardt and the inlier mask.  E and F = K^-T E
+// K^-1 come out under verify_pairs' convention (x2^T F x1 = 0, unit norm, the
+// Sampson distance in pixels), so F goes straight into sfm_init_pairs.  The
+// reference has no counterpart.
+//
+//   k_ep_fit_score  flat grid over (pair, hypothesis tile) from a host prefix
+//                   table, as k_vp_fit_score.  Fit: one thread per hypothesis,
+//                   four lanes of every wave at a time, the 10 x 20 constraint
+//                   matrix in LDS (five_point.hpp).  Score: the pair's
+//                   correspondences are staged through LDS in tiles of 1024 (the
+//                   fit's workspace, reused), a wave per (hypothesis, solution),
+//                   ballot popcount of the inlier rule and a fixed-order sum of
+//                   the inliers' squared distances; empty solution slots are
+//                   skipped wave-uniformly.  Per hypothesis the best solution
+//                   (count, then cost, then the earliest) is written out.
+//   k_ep_refit      one workgroup per pair: the winner (count, then cost, then
+//                   the earliest hypothesis), its mask, then rounds of the
+//                   five-parameter fit over the current inliers (per-thread
+//                   partial sums of the 5 x 5 normal equations, a fixed-order
+//                   tree, the solve by every thread on the same bits), a re-score
+//                   of the whole pair and the not-worse test.
+//
+// Every sum runs in a fixed order over quantities of the pair alone and counts
+// are integers, so a pair's outputs do not depend on the batch it is in.  No
+// float atomics anywhere.
+#include <cmath>
+#include <cstring>
+
+#include "five_point.hpp"
+#include "staging.hpp"
+
+#pragma clang fp contract(off)
+
+namespace sfm {
+
+constexpr int EP_THREADS = 256;                 // fit and score
+constexpr int EP_WAVES = EP_THREADS / 64;
+constexpr int EP_LANES = 4;                     // lanes of a wave that fit at a time
+constexpr int EP_FIT = EP_WAVES * EP_LANES;     // hypotheses fitted per pass
+constexpr int EP_HT = 32;                       // most hypotheses per workgroup
+constexpr int EP_TILE = 1024;                   // correspondences per LDS tile (32 KiB)
+constexpr int EP_SMEM = EP_FIT * EP_WS > 4 * EP_TILE ? EP_FIT * EP_WS : 4 * EP_TILE;  // doubles
+constexpr int EP_RT = 256;                      // refit
+constexpr int EP_RW = EP_RT / 64;
+static_assert(EP_RW == 4, "ep_wg_sum adds four wave results");
+
+// sum over the 64 lanes by a butterfly: both partners add the same pair, so
+// every lane holds the same bits
+__device__ __forceinline__ double ep_wave_sum(double x) {
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) x += __shfl_xor(x, w);
+    return x;
+}
+
+// blk_start (n_live + 1): the first block of each live pair (n_p >= 5); tab
+// (n_live x 2): the pair and the hypotheses per block chosen for it.  Per
+// hypothesis: n_sol; h_count, h_cost, h_E (9) of its best solution (h_count -1
+// without one).  counts (P x H x 10) and models (P x H x 10 x 9) may be null.
+__global__ void __launch_bounds__(EP_THREADS)
+k_ep_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1,
+               const double2 *__restrict__ x2, const int32_t *__restrict__ samples, int32_t H,
+               const int32_t *__restrict__ blk_start, const int32_t *__restrict__ tab, int32_t n_live, EpK K,
+               double thr, int32_t *__restrict__ n_sol, int32_t *__restrict__ h_count, double *__restrict__ h_cost,
+               double *__restrict__ h_E, int32_t *__restrict__ counts, double *__restrict__ models) {
+    __shared__ double smem[EP_SMEM];
+    __shared__ double sE[EP_HT][EP_MAX_SOL][9];
+    __shared__ double sCost[EP_HT][EP_MAX_SOL];
+    __shared__ int32_t sCnt[EP_HT][EP_MAX_SOL], sN[EP_HT];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the live pair of this block: the last j with blk_start[j] <= blockIdx.x
+    int lo = 0, hi = n_live - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk_start[mid] <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const int32_t p = tab[2 * lo], ht = tab[2 * lo + 1];
+    const int32_t hb = ((int32_t)blockIdx.x - blk_start[lo]) * ht;
+    const int nh = min(ht, H - hb);
+    const int64_t ps = pair_start[p];
+    const int n = (int)(pair_start[p + 1] - ps);
+    const int64_t row0 = (int64_t)p * H + hb;
+
+    // ---- fit: 16 hypotheses a pass, one thread each
+    if (lane < EP_LANES) {
+        const int slot = wave * EP_LANES + lane;
+        const EpWs<EP_FIT> w{smem + slot};
+        for (int hl = slot; hl < nh; hl += EP_FIT) {
+            double a[5], b[5], c[5], d[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const int64_t k = ps + samples[(row0 + hl) * 5 + i];
+                const double2 q1 = x1[k], q2 = x2[k];
+                ep_normalise(K, q1.x, q1.y, a[i], b[i]);
+                ep_normalise(K, q2.x, q2.y, c[i], d[i]);
+            }
+            sN[hl] = ep_solve(a, b, c, d, w, &sE[hl][0][0]);
+            for (int s = 0; s < EP_MAX_SOL; ++s) {
+                sCnt[hl][s] = 0;
+                sCost[hl][s] = 0.0;
+            }
+        }
+    }
+    __syncthreads();  // the workspace is free: it becomes the tiles
+
+    // ---- score: a wave per (hypothesis, solution), the pair's tile shared by all of them
+    double2 *s1 = reinterpret_cast<double2 *>(smem), *s2 = s1 + EP_TILE;
+    const double thr2 = thr * thr;
+    for (int base = 0; base < n; base += EP_TILE) {
+        const int nt = min(EP_TILE, n - base);
+        for (int i = tid; i < nt; i += EP_THREADS) {
+            s1[i] = x1[ps + base + i];
+            s2[i] = x2[ps + base + i];
+        }
+        __syncthreads();
+        for (int hl = wave; hl < nh; hl += EP_WAVES) {
+            const int ns = __builtin_amdgcn_readfirstlane(sN[hl]);
+            for (int s = 0; s < ns; ++s) {
+                double E[9], F[9];
+#pragma unroll
+                for (int j = 0; j < 9; ++j) E[j] = sE[hl][s][j];
+                ep_F(K, E, F);
+                int cnt = 0;
+                double acc = 0.0;
+                for (int j = 0; j < nt; j += 64) {
+                    const int i = j + lane;
+                    bool in = false;
+                    if (i < nt) {
+                        const double2 q1 = s1[i], q2 = s2[i];
+                        double e2, den;
+                        in = vp_inlier(F, q1.x, q1.y, q2.x, q2.y, thr2, e2, den);
+                        if (in) acc += e2 / den;
+                    }
+                    cnt += __popcll(__ballot(in));
+                }
+                acc = ep_wave_sum(acc);
+                if (lane == 0) {  // this wave alone owns hl
+                    sCnt[hl][s] += cnt;
+                    sCost[hl][s] += acc;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- the best solution of each hypothesis
+    if (tid < nh) {
+        const int ns = sN[tid];
+        int bs = 0, bc = -1;
+        double bcost = 0.0;
+        for (int s = 0; s < ns; ++s) {
+            const int c = sCnt[tid][s];
+            const double co = sCost[tid][s];
+            if (c > bc || (c == bc && co < bcost)) { bc = c; bcost = co; bs = s; }
+        }
+        n_sol[row0 + tid] = ns;
+        h_count[row0 + tid] = bc;
+        h_cost[row0 + tid] = bcost;
+        for (int j = 0; j < 9; ++j) h_E[(row0 + tid) * 9 + j] = ns > 0 ? sE[tid][bs][j] : 0.0;
+        if (counts)
+            for (int s = 0; s < EP_MAX_SOL; ++s) counts[(row0 + tid) * EP_MAX_SOL + s] = s < ns ? sCnt[tid][s] : 0;
+        if (models)
+            for (int s = 0; s < EP_MAX_SOL; ++s)
+                for (int j = 0; j < 9; ++j)
+                    models[((row0 + tid) * EP_MAX_SOL + s) * 9 + j] = s < ns ? sE[tid][s][j] : 0.0;
+    }
+}
+
+// ------------------------------------------------------------------ phase 2
+// Fixed-order sum of NV values over the workgroup: the butterfly within a wave,
+// then the four wave results as (0 + 1) + (2 + 3).  red: EP_RW x NV.
+template <int NV>
+__device__ __forceinline__ void ep_wg_sum(double (&x)[NV], double (*red)[NV]) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) x[j] = ep_wave_sum(x[j]);
+    __syncthreads();  // the last use of red is over
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) red[threadIdx.x >> 6][j] = x[j];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) x[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+}
+
+struct EpPair {
+    const double2 *x1, *x2;  // the pair's first correspondence
+    int n;
+};
+
+// mask[i] = the inlier rule under F for the pair's correspondence i; count and
+// the inliers' squared Sampson distances summed (thread t owns i = t, t + 256, ...)
+__device__ __forceinline__ void ep_mask(const EpPair &w, const double *F, double thr2, uint8_t *mask, int &count,
+                                        double &cost, double (*red)[2]) {
+    double acc[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < w.n; i += EP_RT) {
+        const double2 p = w.x1[i], q = w.x2[i];
+        double e2, den;
+        const bool in = vp_inlier(F, p.x, p.y, q.x, q.y, thr2, e2, den);
+        mask[i] = in ? 1 : 0;
+        if (in) {
+            acc[0] += 1.0;
+            acc[1] += e2 / den;
+        }
+    }
+    ep_wg_sum<2>(acc, red);
+    count = (int)acc[0];
+    cost = acc[1];
+}
+
+// (count, cost, hypothesis): more inliers, then the smaller cost, then the earlier
+__device__ __forceinline__ void ep_merge(int32_t &c1, double &s1, int32_t &h1, int32_t c2, double s2, int32_t h2) {
+    if (c2 > c1 || (c2 == c1 && (s2 < s1 || (s2 == s1 && h2 < h1)))) {
+        c1 = c2;
+        s1 = s2;
+        h1 = h2;
+    }
+}
+
+// One workgroup per pair.  mask2: scratch of n_corr bytes.  Pairs of fewer than
+// five correspondences are the host's (info -1): nothing of them is read.
+__global__ void __launch_bounds__(EP_RT)
+k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1, const double2 *__restrict__ x2,
+           int32_t H, EpK K, double thr, int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev,
+           const int32_t *__restrict__ h_count, const double *__restrict__ h_cost, const double *__restrict__ h_E,
+           uint8_t *mask2, double *__restrict__ E_out, double *__restrict__ F_out, double *__restrict__ cost_out,
+           int32_t *__restrict__ n_inl_out, int32_t *__restrict__ hyp_out, int32_t *__restrict__ count_out,
+           int32_t *__restrict__ info_out, uint8_t *inlier) {
+    __shared__ int32_t sc[EP_RW], sh[EP_RW];
+    __shared__ double ss[EP_RW];
+    __shared__ double red[EP_RW][EP_NV];
+    __shared__ double red2[EP_RW][2];
+    const int tid = threadIdx.x;
+    const int64_t p = blockIdx.x;
+    const int64_t ps = pair_start[p];
+    const int n = (int)(pair_start[p + 1] - ps);
+    if (n < 5) return;
+    const EpPair w{x1 + ps, x2 + ps, n};
+    uint8_t *mask = inlier + ps, *trial = mask2 + ps;
+    const double thr2 = thr * thr;
+
+    // ---- the winner over the hypotheses' best solutions
+    int32_t bc = -1, bh = 0x7fffffff;
+    double bs = 0.0;
+    for (int32_t h = tid; h < H; h += EP_RT) {
+        const int32_t c = h_count[p * H + h];
+        if (c >= 0) ep_merge(bc, bs, bh, c, h_cost[p * H + h], h);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int32_t c2 = __shfl_xor(bc, off), h2 = __shfl_xor(bh, off);
+        const double s2 = __shfl_xor(bs, off);
+        ep_merge(bc, bs, bh, c2, s2, h2);
+    }
+    if ((tid & 63) == 0) { sc[tid >> 6] = bc; ss[tid >> 6] = bs; sh[tid >> 6] = bh; }
+    __syncthreads();
+    bc = sc[0]; bs = ss[0]; bh = sh[0];
+#pragma unroll
+    for (int k = 1; k < EP_RW; ++k) ep_merge(bc, bs, bh, sc[k], ss[k], sh[k]);
+
+    double E[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double cost = 0.0;
+    int info = -2, n_inl = 0;
+    if (bc < 0) {
+        for (int i = tid; i < n; i += EP_RT) mask[i] = 0;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) E[j] = h_E[(p * H + bh) * 9 + j];
+        ep_F(K, E, F);
+        ep_mask(w, F, thr2, mask, n_inl, cost, red2);
+        info = -3;
+        if (bc >= min_inliers) {
+            info = 0;
+            // the sums of the normal equations over the current inliers; every thread gets the same bits
+            const auto eval = [&](const double (&R)[9], const double (&t)[3], double (&A)[15], double (&g)[5],
+                                  double &c) {
+                EpModel m;
+                ep_model(K, R, t, m);
+                double s[EP_NV];
+#pragma unroll
+                for (int j = 0; j < EP_NV; ++j) s[j] = 0.0;
+                for (int i = tid; i < n; i += EP_RT) {
+                    if (!mask[i]) continue;
+                    const double2 q1 = w.x1[i], q2 = w.x2[i];
+                    ep_accum(m, q1.x, q1.y, q2.x, q2.y, s);
+                }
+                ep_wg_sum<EP_NV>(s, red);
+#pragma unroll
+                for (int j = 0; j < 15; ++j) A[j] = s[j];
+#pragma unroll
+                for (int j = 0; j < 5; ++j) g[j] = s[15 + j];
+                c = s[21] > 0.0 ? INFINITY : s[20];
+            };
+            for (int round = 0; round < refit_rounds; ++round) {
+                double R[9], t[3];
+                if (!ep_factor(E, R, t)) {
+                    info = -4;
+                    break;
+                }
+                info = ep_lm(eval, R, t, max_nfev);
+                if (info < 0) break;
+                double G[9], En[9], Fn[9], cost2;
+                int n2;
+                ep_cross_mat(t, R, G);
+                vp_unit(G, En);
+                ep_F(K, En, Fn);
+                ep_mask(w, Fn, thr2, trial, n2, cost2, red2);
+                // the refitted state replaces the current one only if it is not worse
+                if (!(n2 > n_inl || (n2 == n_inl && cost2 <= cost))) break;
+                int changed = 0;
+                for (int i = tid; i < n; i += EP_RT) {
+                    changed |= mask[i] != trial[i];
+                    mask[i] = trial[i];
+                }
+                changed = __syncthreads_or(changed);
+#pragma unroll
+                for (int j = 0; j < 9; ++j) { E[j] = En[j]; F[j] = Fn[j]; }
+                n_inl = n2;
+                cost = cost2;
+                if (!changed) break;
+            }
+        }
+    }
+    if (tid == 0) {
+        for (int j = 0; j < 9; ++j) {
+            E_out[9 * p + j] = E[j];
+            F_out[9 * p + j] = F[j];
+        }
+        cost_out[p] = cost;
+        n_inl_out[p] = n_inl;
+        hyp_out[p] = bc < 0 ? -1 : bh;
+        count_out[p] = bc < 0 ? 0 : bc;
+        info_out[p] = info;
+    }
+}
+
+}  // namespace sfm
+
+using namespace sfm;
+
+extern "C" int sfm_essential_pairs(const double *K, const int64_t *pair_start, int64_t P, const double *x1,
+                                   const double *x2, int64_t n_corr, const int32_t *samples, int64_t H,
+                                   double threshold, int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev,
+                                   double *E, double *F, double *cost, int32_t *n_inliers, int32_t *best_hyp,
+                                   int32_t *best_count, int32_t *info, uint8_t *inlier, int32_t *n_sol,
+                                   int32_t *counts, double *models, int device) {
+    SFM_CHECK_ARG(P >= 0 && n_corr >= 0, "P < 0 or n_corr < 0");
+    SFM_CHECK_ARG(H >= 1 && H <= (int64_t)1 << 20, "H must lie in [1, 2^20]");
+    SFM_CHECK_ARG(std::isfinite(threshold) && threshold > 0.0, "threshold must be finite and positive");
+    SFM_CHECK_ARG(min_inliers >= 5, "min_inliers must be at least 5");
+    SFM_CHECK_ARG(refit_rounds >= 0, "refit_rounds < 0");
+    SFM_CHECK_ARG(max_nfev > 0, "max_nfev must be positive");
+    SFM_CHECK_ARG(P < (int64_t)0x7fffffff / (H * EP_MAX_SOL), "P x H too large for one call");
+    SFM_CHECK_ARG(K && pair_start, "null pointer");
+    for (int j = 0; j < 9; ++j) SFM_CHECK_ARG(std::isfinite(K[j]), "K is not finite");
+    // K^-1 by the adjugate
+    EpK Ki;
+    {
+        const double c00 = K[4] * K[8] - K[5] * K[7], c01 = K[5] * K[6] - K[3] * K[8], c02 = K[3] * K[7] - K[4] * K[6];
+        const double det = (K[0] * c00 + K[1] * c01) + K[2] * c02;
+        SFM_CHECK_ARG(std::isfinite(det) && det != 0.0, "K is singular");
+        const double adj[9] = {c00, K[2] * K[7] - K[1] * K[8], K[1] * K[5] - K[2] * K[4],
+                               c01, K[0] * K[8] - K[2] * K[6], K[2] * K[3] - K[0] * K[5],
+                               c02, K[1] * K[6] - K[0] * K[7], K[0] * K[4] - K[1] * K[3]};
+        for (int j = 0; j < 9; ++j) {
+            Ki.ki[j] = adj[j] / det;
+            SFM_CHECK_ARG(std::isfinite(Ki.ki[j]), "K has no finite inverse");
+        }
+    }
+    SFM_TRY(check_csr(pair_start, P, n_corr, "pair_start", "correspondence", 0x7fffffff,
+                      "a pair has too many correspondences"));
+    int64_t n_live = 0;
+    for (int64_t p = 0; p < P; ++p) n_live += pair_start[p + 1] - pair_start[p] >= 5;
+    SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
+    SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t n = pair_start[p + 1] - pair_start[p];
+        if (n < 5) continue;
+        const int32_t *sp = samples + p * H * 5;
+        for (int64_t h = 0; h < H; ++h) {
+            const int32_t *s = sp + h * 5;
+            for (int a = 0; a < 5; ++a) {
+                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_p)");
+                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
+            }
+        }
+    }
+    if (P == 0) return 0;
+    SFM_CHECK_ARG(E && F && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
+                  "null pointer");
+    // info -1: fewer than five correspondences
+    for (int64_t p = 0; p < P; ++p) {
+        if (pair_start[p + 1] - pair_start[p] >= 5) continue;
+        for (int j = 0; j < 9; ++j) {
+            E[9 * p + j] = 0.0;
+            F[9 * p + j] = 0.0;
+        }
+        cost[p] = 0.0;
+        n_inliers[p] = 0;
+        best_hyp[p] = -1;
+        best_count[p] = 0;
+        info[p] = -1;
+        for (int64_t k = pair_start[p]; k < pair_start[p + 1]; ++k) inlier[k] = 0;
+        if (n_sol) std::memset(n_sol + p * H, 0, (size_t)H * sizeof(int32_t));
+        if (counts) std::memset(counts + p * H * EP_MAX_SOL, 0, (size_t)H * EP_MAX_SOL * sizeof(int32_t));
+        if (models) std::memset(models + p * H * EP_MAX_SOL * 9, 0, (size_t)H * EP_MAX_SOL * 9 * sizeof(double));
+    }
+    if (n_live == 0) return 0;
+
+    ThreadCtx *c = thread_ctx(device);
+    if (!c) return SFM_ERR_HIP;
+    int rc;
+    // block table: a pair of many correspondences gets fewer hypotheses per
+    // block, so that its score loop is spread over more of them
+    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
+    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
+    int64_t blocks = 0, j = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t n = pair_start[p + 1] - pair_start[p];
+        if (n < 5) continue;
+        const int32_t ht = n >= 4 * EP_TILE ? EP_HT / 4 : (n >= EP_TILE ? EP_HT / 2 : EP_HT);
+        blk[j] = (int32_t)blocks;
+        tab[2 * j] = (int32_t)p;
+        tab[2 * j + 1] = ht;
+        blocks += (H + ht - 1) / ht;
+        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
+        ++j;
+    }
+    blk[n_live] = (int32_t)blocks;
+
+    const size_t PH = (size_t)P * (size_t)H;
+    Pack in(c->buf[0]), out(c->buf[1]);
+    const auto i_ps = in.add<int64_t>(P + 1);
+    const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
+    const auto i_s = in.add<int32_t>(5 * PH);
+    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto o_E = out.add<double>(9 * P), o_F = out.add<double>(9 * P), o_cost = out.add<double>(P);
+    const auto o_info = out.add<int32_t>(P), o_ninl = out.add<int32_t>(P);
+    const auto o_hyp = out.add<int32_t>(P), o_bc = out.add<int32_t>(P);
+    const auto o_ns = out.add<int32_t>(PH), o_hc = out.add<int32_t>(PH);
+    const auto o_hs = out.add<double>(PH), o_hE = out.add<double>(9 * PH);
+    // the per-solution tables exist on the device only when they are asked for
+    const auto o_cnt = out.add<int32_t>(counts ? EP_MAX_SOL * PH : 0);
+    const auto o_m = out.add<double>(models ? 9 * EP_MAX_SOL * PH : 0);
+    const auto o_mask = out.add<uint8_t>(n_corr), o_m2 = out.add<uint8_t>(n_corr);  // o_m2: the refits' trial mask
+    SFM_TRY(in.reserve());
+    SFM_TRY(out.reserve());
+    hipStream_t s = c->stream;
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(in.upload(i_ps, pair_start, s));
+    SFM_TRY(in.upload(i_x1, x1, s));
+    SFM_TRY(in.upload(i_x2, x2, s));
+    SFM_TRY(in.upload(i_s, samples, s));
+    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(tm.mark(s));
+    hipLaunchKernelGGL(k_ep_fit_score, dim3((unsigned)blocks), dim3(EP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
+                       in.ptr(i_x2), in.ptr(i_s), (int32_t)H, in.ptr(i_t), in.ptr(i_t, n_live + 1), (int32_t)n_live,
+                       Ki, threshold, out.ptr(o_ns), out.ptr(o_hc), out.ptr(o_hs), out.ptr(o_hE),
+                       counts ? out.ptr(o_cnt) : nullptr, models ? out.ptr(o_m) : nullptr);
+    SFM_HIP(hipGetLastError());
+    SFM_TRY(tm.split(s));  // [3]: the fit-and-score kernel alone
+    hipLaunchKernelGGL(k_ep_refit, dim3((unsigned)P), dim3(EP_RT), 0, s, in.ptr(i_ps), in.ptr(i_x1), in.ptr(i_x2),
+                       (int32_t)H, Ki, threshold, min_inliers, refit_rounds, max_nfev, out.ptr(o_hc), out.ptr(o_hs),
+                       out.ptr(o_hE), out.ptr(o_m2), out.ptr(o_E), out.ptr(o_F), out.ptr(o_cost), out.ptr(o_ninl),
+                       out.ptr(o_hyp), out.ptr(o_bc), out.ptr(o_info), out.ptr(o_mask));
+    SFM_HIP(hipGetLastError());
+    SFM_TRY(tm.mark(s));
+    // live pairs are copied out one run of consecutive pairs at a time, so that
+    // what the host wrote for the pairs of info -1 stays
+    for (int64_t p0 = 0; p0 < P;) {
+        if (pair_start[p0 + 1] - pair_start[p0] < 5) {
+            ++p0;
+            continue;
+        }
+        int64_t p1 = p0;
+        while (p1 < P && pair_start[p1 + 1] - pair_start[p1] >= 5) ++p1;
+        const size_t np = (size_t)(p1 - p0);
+        SFM_TRY(out.download(E + 9 * p0, o_E, 9 * p0, 9 * np, s));
+        SFM_TRY(out.download(F + 9 * p0, o_F, 9 * p0, 9 * np, s));
+        SFM_TRY(out.download(cost + p0, o_cost, p0, np, s));
+        SFM_TRY(out.download(info + p0, o_info, p0, np, s));
+        SFM_TRY(out.download(n_inliers + p0, o_ninl, p0, np, s));
+        SFM_TRY(out.download(best_hyp + p0, o_hyp, p0, np, s));
+        SFM_TRY(out.download(best_count + p0, o_bc, p0, np, s));
+        const int64_t k0 = pair_start[p0], k1 = pair_start[p1];
+        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
+        if (n_sol) SFM_TRY(out.download(n_sol + p0 * H, o_ns, p0 * H, np * H, s));
+        if (counts)
+            SFM_TRY(out.download(counts + p0 * H * EP_MAX_SOL, o_cnt, p0 * H * EP_MAX_SOL, np * H * EP_MAX_SOL, s));
+        if (models)
+            SFM_TRY(out.download(models + p0 * H * EP_MAX_SOL * 9, o_m, p0 * H * EP_MAX_SOL * 9,
+                                 np * H * EP_MAX_SOL * 9, s));
+        p0 = p1;
+    }
+    return tm.finish(s);
+}

@@ -125,6 +125,32 @@ def verify_pairs(store, images=None, H=256, seed=0, threshold=2.5, min_inliers=8
     return order, pair_ij, out, index1, index2
 
 
+def verify_pairs_calibrated(store, K, images=None, H=256, seed=0, threshold=2.5, min_inliers=8, min_matches=8,
+                            update_flags=False):
+    """``verify_pairs`` with the calibration: the essential matrix of every
+    image pair of ``store`` over ``images`` (default all) in one device call
+    (``_sfmcore.essential_pairs``: 5-point RANSAC over H hypotheses per pair,
+    scored in pixels by the Sampson distance of F = K^-T E K^-1, the winner
+    refitted as E = [t]x R on its consensus set).  Unlike the 8-point F it has a
+    model for a pair that looks at one plane, and its E is an essential matrix.
+    Returns (order, pair_ij, out, index1, index2) with ``verify_pairs``'s
+    meaning; ``out`` is (F, cost, n_inliers, inlier, best_hyp, best_count, info,
+    E): positions 0-6 are what ``init_pairs`` reads, so
+    ``init_pairs(store, K, verified)`` works on the result unchanged.
+    ``update_flags`` as in ``verify_pairs``."""
+    pair_ij, pair_start, index1, index2 = store.pairs(images, min_matches=min_matches)
+    x1 = np.column_stack([store.x[index1], store.y[index1]])
+    x2 = np.column_stack([store.x[index2], store.y[index2]])
+    samples = _core.essential_samples(np.diff(pair_start), H, seed)
+    out = _core.essential_pairs(K, pair_start, x1, x2, samples, threshold=threshold, min_inliers=min_inliers)
+    order = np.argsort(-out[2].astype(np.int64), kind="stable")
+    if update_flags:
+        ok = np.repeat(out[6] >= 0, np.diff(pair_start)) & out[3]
+        store.flag[index1[ok]] = 1
+        store.flag[index2[ok]] = 1
+    return order, pair_ij, out, index1, index2
+
+
 def init_pairs(store, K, verified, Hh=128, seed=0, h_threshold=4.0, max_reproj=4.0, min_points=30, min_angle_deg=4.0,
                max_h_ratio=0.8):
     """Which pair to start the reconstruction from, and with what pose and
