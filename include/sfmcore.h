@@ -366,6 +366,78 @@ int sfm_register_views(const double *K, const double *X, int64_t n_pts, const in
                        int device);
 
 /* ---------------------------------------------------------------------
+ * Calibrated batched view registration: sfm_register_views with the minimal
+ * solver of a calibrated camera, 3-point samples and up to four poses per
+ * hypothesis (the reference has no counterpart).  It registers views whose
+ * points lie on one plane, where the 12 x 12 DLT system of sfm_register_views
+ * has a four-dimensional null space.
+ * K, X, view_start, pt_idx, xy: as sfm_register_views, under the same rules.
+ * samples (V x H x 3): each entry a position inside its view, in [0, n_v), the
+ * three of a hypothesis distinct; ignored for views of n_v < 4.  1 <= H <=
+ * 2^20; threshold in pixels, finite and > 0; min_inliers >= 4 (a view of three
+ * correspondences fits every solution exactly and decides nothing);
+ * refit_rounds >= 0; max_nfev > 0.  A violation is SFM_ERR_ARG, found on the
+ * host before a device is looked for; no output is touched.
+ * Hypothesis: bearings b_i = K^-1 [x_i; 1], normalised.  Every pose (R, C) with
+ * det R = +1 is a solution for which R (X_i - C) is a positive multiple of b_i
+ * for the three sampled correspondences and which is finite; there are up to
+ * four, n_sol (V x H) counts them.  Their set is specified, their order is not.
+ * Method (csrc/p3p.hpp): with a_ij = |X_i - X_j|^2 / extent^2 (extent the
+ * largest of the three distances) and c_ij = b_i . b_j the depths d_i satisfy
+ * d_i^2 + d_j^2 - 2 c_ij d_i d_j = a_ij; the real roots of the cubic det(D1 + g
+ * D2) = 0 of the two homogeneous combinations D1, D2 of these quadrics are
+ * found (one by Newton's method from a bound it approaches monotonically, the
+ * other two from the remaining quadratic, real where its discriminant is >= 0)
+ * and polished by two Newton steps; the root whose
+ * degenerate quadric is most clearly a pair of real planes is taken, and each
+ * plane cuts the other quadric of the pencil in a homogeneous quadratic.  A
+ * root of a quadratic counts as real where its discriminant is >= 0 in fp64.
+ * Every candidate is polished by five Gauss-Newton steps on the three distance
+ * constraints and kept where its depths are finite and positive and every
+ * constraint holds to 1e-10 (of a_ij <= 1) afterwards, so that a root that is
+ * real by rounding alone is dropped.  R maps the orthonormal frame of the
+ * triangle X to that of the triangle d_i b_i; C = mean X - R^T mean(d b).
+ * A sample has no solutions (n_sol = 0, no error) where two of its points lie
+ * within 1e-12 of the sample's extent of each other or its three points are
+ * collinear in space (|(X_2 - X_1) x (X_3 - X_1)| <= 1e-10 extent^2).
+ * Score: every solution under P = K [R | -R C], the pose itself (`models`),
+ * with sfm_register_views' inlier rule: with h = P [X; 1], h2 > 0, not |h2| <
+ * 1e-8 and (u - h0/h2)^2 + (v - h1/h2)^2 < threshold^2 (the fp64 expression
+ * decides).  The winner over all (hypothesis, solution) pairs has the most
+ * inliers, then the smaller sum of its inliers' squared errors, then the
+ * earlier hypothesis, then the earlier solution.  The cost is formed only for
+ * the solutions that tie on the best count, one pass over the view's
+ * correspondences each in the view's one workgroup: the winner's selection
+ * costs (1 + ties) passes, up to 4 H of them where every solution of every
+ * hypothesis has the best count (a noise-free view).
+ * Refit: sfm_register_views' own, started from the winning solution's pose: LM
+ * on six pose parameters over the current inliers under the same control and
+ * stop codes, the re-score of the whole view, the not-worse rule, up to
+ * refit_rounds rounds.  So n_inliers >= best_count.
+ * Outputs per view: C, R, cost, n_inliers, best_hyp (the winner's hypothesis,
+ * -1 without one), best_count, info as sfm_register_views with -1 n_v < 4 (C =
+ * 0, R = I, nothing an inlier; nothing of the view is read on or from the
+ * device), -2 no solution in any hypothesis (the same outputs), -3 best_count <
+ * min_inliers (the winning solution's pose, mask, count and cost, no refit),
+ * -4 the refit's start had no finite cost (as -3).  Per correspondence: inlier
+ * (n_corr), 1 or 0.  Nullable: n_sol (V x H), counts (V x H x 4) the inliers
+ * per solution, models (V x H x 4 x 12) the projections; counts and models are
+ * zero in the slots past n_sol, and all three are zero for a view of n_v < 4.
+ * No sum depends on the batch and there are no float atomics: a view's outputs
+ * are the same bits alone, in any batch and at any place in it, and a
+ * hypothesis's n_sol, counts and models do not depend on H.  Two launches and
+ * one synchronisation whatever V is; V == 0, or no view of four
+ * correspondences, returns without touching a device.  sfm_last_timings:
+ * upload, both kernels, download, the fit-and-score kernel alone.
+ * ------------------------------------------------------------------- */
+int sfm_register_views_p3p(const double *K, const double *X, int64_t n_pts, const int64_t *view_start, int64_t V,
+                           const int32_t *pt_idx, const double *xy, int64_t n_corr, const int32_t *samples,
+                           int64_t H, double threshold, int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev,
+                           double *C, double *R, double *cost, int32_t *n_inliers, int32_t *best_hyp,
+                           int32_t *best_count, int32_t *info, uint8_t *inlier, int32_t *n_sol, int32_t *counts,
+                           double *models, int device);
+
+/* ---------------------------------------------------------------------
  * Batched pair verification: 8-point F-RANSAC and a least-squares refit for
  * every image pair in one call, under one convention, x2^T F x1 = 0 (the
  * reference verifies one pair per call, Wrapper_dev.py:69-123, with a design

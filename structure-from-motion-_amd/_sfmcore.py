@@ -105,6 +105,9 @@ SIGNATURES = [
     ("sfm_register_views", _c, [_d, _d, _i, _i64, _i, _i32, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32,
                                 ctypes.c_int32, ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32, _d,
                                 _c]),
+    ("sfm_register_views_p3p", _c, [_d, _d, _i, _i64, _i, _i32, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32,
+                                    ctypes.c_int32, ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32,
+                                    _i32, _d, _c]),
     ("sfm_verify_pairs", _c, [_i64, _i, _d, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _d,
                               _d, _i32, _i32, _i32, _i32, _u8, _i32, _d, _c]),
     ("sfm_essential_pairs", _c, [_d, _i64, _i, _d, _d, _i, _i32, _i, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
@@ -827,6 +830,14 @@ def register_samples(counts, H, seed):
     return _sample_tables(counts, H, seed, 6, "register_samples")
 
 
+def p3p_samples(counts, H, seed):
+    """The 3-point sample table of register_views_p3p: (V, H, 3) int32, drawn
+    as register_samples draws -- view v from child v of
+    numpy.random.default_rng(seed), the rows that hold a duplicate redrawn until
+    none do; a view of n_v < 3 gets zeros."""
+    return _sample_tables(counts, H, seed, 3, "p3p_samples")
+
+
 def _sample_tables(counts, H, seed, k, who):
     """(len(counts), H, k) int32: row v from child v of the seed, k distinct
     positions in [0, counts[v]) per hypothesis, zeros where counts[v] < k"""
@@ -1137,6 +1148,65 @@ def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inl
         out += (counts,)
     if want_models:
         out += (models.reshape(V, H, 3, 4),)
+    return out
+
+
+def register_views_p3p(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=4, refit_rounds=3,
+                       max_nfev=50, want_counts=False, want_models=False):
+    """Calibrated batched view registration (sfm_register_views_p3p): for every
+    view, P3P RANSAC over the host-drawn ``samples`` (V, H, 3; p3p_samples) --
+    up to four poses per sample, each scored as P = K [R | -R C] -- then
+    register_views' refit from the winning pose.  Unlike register_views it
+    registers views of points on one plane.  X, view_start, pt_idx, xy as
+    register_views.  Returns register_views' eight outputs in the same places
+    (C, R, cost, n_inliers, inlier, best_hyp, best_count, info; info -1 is
+    fewer than four correspondences, -2 no solution in any hypothesis), then
+    n_sol (V, H) and counts (V, H, 4) int32 with want_counts and models (V, H,
+    4, 3, 4) with want_models, zero past n_sol.  The arguments are checked
+    before a device is looked for; V = 0, or no view of four correspondences,
+    returns without one."""
+    K = _f64(K).reshape(3, 3)
+    X = _f64(X).reshape(-1, 3)
+    vs = np.ascontiguousarray(view_start, dtype=np.int64).reshape(-1)
+    pt = np.ascontiguousarray(pt_idx, dtype=np.int32).reshape(-1)
+    xy = _f64(xy).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    if len(vs) < 1 or len(xy) != len(pt):
+        raise ValueError("register_views_p3p: view_start needs V + 1 entries and pt_idx, xy one row per "
+                         "correspondence")
+    V = len(vs) - 1
+    if samples.ndim != 3 or samples.shape[0] != V or samples.shape[2] != 3 or samples.shape[1] < 1:
+        raise ValueError("register_views_p3p: samples must be (V, H, 3) with H >= 1")
+    H = samples.shape[1]
+    threshold = float(threshold)
+    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 4 or int(refit_rounds) < 0
+           or int(max_nfev) <= 0 or H > 1 << 20 or not _csr_ok(vs, pt, len(X)))
+    if not bad:
+        n_v = np.diff(vs)
+        live = n_v >= 4
+        if live.any():
+            s = samples[live]
+            srt = np.sort(s, axis=2)
+            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_v[live]).any()
+                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
+            if not bad:
+                require_device()
+    C, R, cost = np.zeros((V, 3)), np.zeros((V, 9)), np.zeros(V)
+    n_inl, hyp, count, info = (np.zeros(V, dtype=np.int32) for _ in range(4))
+    inlier = np.zeros(len(pt), dtype=np.uint8)
+    n_sol = np.zeros((V, H), dtype=np.int32) if want_counts else None
+    counts = np.zeros((V, H, 4), dtype=np.int32) if want_counts else None
+    models = np.zeros((V, H, 4, 12)) if want_models else None
+    _check(_lib.sfm_register_views_p3p(
+        _p(K), _p(X), len(X), _p(vs, _i64), V, _p(pt, _i32), _p(xy), len(pt), _p(samples, _i32), H, threshold,
+        int(min_inliers), int(refit_rounds), int(max_nfev), _p(C), _p(R), _p(cost), _p(n_inl, _i32), _p(hyp, _i32),
+        _p(count, _i32), _p(info, _i32), _p(inlier, _u8), _p(n_sol, _i32) if want_counts else None,
+        _p(counts, _i32) if want_counts else None, _p(models) if want_models else None, DEVICE))
+    out = (C, R.reshape(V, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info)
+    if want_counts:
+        out += (n_sol, counts)
+    if want_models:
+        out += (models.reshape(V, H, 4, 3, 4),)
     return out
 
 

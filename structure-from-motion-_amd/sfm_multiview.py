@@ -94,6 +94,26 @@ def register_views(store, K, feature_rows, X, candidates, H=256, seed=0, thresho
     return order, out, index
 
 
+def register_views_p3p(store, K, feature_rows, X, candidates, H=256, seed=0, threshold=4.0, min_inliers=4,
+                       update_flags=False):
+    """``register_views`` with the calibrated minimal solver
+    (``_sfmcore.register_views_p3p``: P3P RANSAC over H 3-point samples per
+    view, up to four poses per sample).  Use it where K is trusted: it needs
+    half the points per sample and registers views of points on one plane,
+    which the 6-point DLT cannot.  Same arguments, same (order, out, index)
+    with the same meaning; code that consumes ``register_views`` works on it
+    unchanged."""
+    view_start, pt_idx, xy, index = store.correspondences(feature_rows, candidates)
+    samples = _core.p3p_samples(np.diff(view_start), H, seed)
+    out = _core.register_views_p3p(K, X, view_start, pt_idx, xy, samples, threshold=threshold,
+                                   min_inliers=min_inliers)
+    order = np.argsort(-out[3].astype(np.int64), kind="stable")
+    if update_flags:
+        registered = np.repeat(out[7] >= 1, np.diff(view_start))
+        store.flag[index[registered & ~out[4]]] = 0
+    return order, out, index
+
+
 def verify_pairs(store, images=None, H=256, seed=0, threshold=2.5, min_inliers=8, min_matches=8,
                  update_flags=False):
     """The first stage of the pipeline: the epipolar geometry of every image
