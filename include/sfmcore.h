@@ -637,6 +637,55 @@ int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_t P, const 
                    uint8_t *good, double *angle, double *cands, int32_t *hcounts, double *hmodels, int device);
 
 /* ---------------------------------------------------------------------
+ * Track merging: the rows of a match store that share a keypoint joined into
+ * tracks, on the device.  A matching-file line lists only the direct matches
+ * of one keypoint of its source image, so one scene point arrives as several
+ * rows; this is the track-building step between matching and geometry.  The
+ * reference has no counterpart.
+ * The n_rows rows are CSR rows of the feature-major store: row r owns
+ * observations [row_start[r], row_start[r+1]) of image (0-based), x and y.
+ * Definitions, from which every output follows:
+ *   keypoint of an observation: the smallest observation index with the same
+ *     image and the same x and y as doubles (bit patterns, -0.0 taken as +0.0);
+ *   component of a row: the smallest row index reachable from it, two rows
+ *     being joined when they contain the same keypoint;
+ *   conflicting component: one that contains two different keypoints of one
+ *     image (a single row that lists an image twice with different coordinates
+ *     is one as well);
+ *   label of a row: its component when that is not conflicting; otherwise -1
+ *     under SFM_MERGE_DROP and the row's own index under SFM_MERGE_KEEP_ROWS
+ *     (the row stays the track it was);
+ *   tracks: the distinct non-negative labels, ascending; a track's
+ *     observations are the distinct keypoints of the rows that carry its label,
+ *     ordered by (image, keypoint index).
+ * Outputs, caller-allocated, every one but n_tracks nullable: keypoint (n_obs);
+ * component, conflict (1 or 0) and label (n_rows each); *n_tracks; track_label
+ * and track_start (room for n_rows and n_rows + 1 entries, the first n_tracks
+ * and n_tracks + 1 written); track_obs (room for n_obs keypoint indices, the
+ * first track_start[n_tracks] written: track t owns [track_start[t],
+ * track_start[t+1])); obs_slot (n_obs): the position in track_obs of the
+ * observation's keypoint inside its row's track, -1 for a dropped row.
+ * SFM_ERR_ARG, found on the host with nothing written: row_start not starting
+ * at 0, decreasing or not ending at n_obs; an image outside [0, n_images); a
+ * coordinate that is not finite; an unknown policy; more than 2^30 rows or
+ * observations, or bits(n_rows) + bits(n_images) + bits(n_obs) > 64 (the order
+ * inside the tracks comes from one 64-bit radix sort).  n_rows == 0 succeeds
+ * with no track and n_obs == 0 with one empty track per row, without a device.
+ * Integer work throughout: every output is the same from run to run and does
+ * not depend on the order in which threads arrive (every choice is a minimum or
+ * a sorted order).  No thread waits for another; a conflicting row that is
+ * kept is searched linearly for its repeated keypoints, so rows are expected
+ * to be short (at most one observation per image in a parsed store).
+ * sfm_last_timings: upload, kernels, download.
+ * ------------------------------------------------------------------- */
+enum { SFM_MERGE_DROP = 0, SFM_MERGE_KEEP_ROWS = 1 };
+int sfm_merge_tracks(const int64_t *row_start, int64_t n_rows, const int32_t *image, const double *x,
+                     const double *y, int64_t n_obs, int32_t n_images, int32_t policy, int32_t *keypoint,
+                     int32_t *component, uint8_t *conflict, int32_t *label, int64_t *n_tracks,
+                     int32_t *track_label, int64_t *track_start, int32_t *track_obs, int32_t *obs_slot,
+                     int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

@@ -114,6 +114,8 @@ SIGNATURES = [
                                  ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32, _i32, _d, _c]),
     ("sfm_init_pairs", _c, [_d, _i64, _i, _d, _d, _i, _d, _i32, _i, ctypes.c_double, ctypes.c_double, _d, _d, _i64,
                             _i32, _i32, _d, _i32, _i32, _d, _i32, _d, _u8, _d, _d, _i32, _d, _c]),
+    ("sfm_merge_tracks", _c, [_i64, _i, _i32, _d, _d, _i, ctypes.c_int32, ctypes.c_int32, _i32, _i32, _u8, _i32, _i64,
+                              _i32, _i64, _i32, _i32, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -1090,6 +1092,52 @@ def init_pairs(K, pair_start, x1, x2, F, hsamples=None, h_threshold=4.0, max_rep
     if want_hmodels:
         out += (hmodels.reshape(P, Hh, 3, 3),)
     return out
+
+
+MERGE_DROP, MERGE_KEEP_ROWS = 0, 1
+
+
+def merge_tracks(row_start, image, x, y, n_images, policy=MERGE_DROP):
+    """Track merging (sfm_merge_tracks): the rows of a feature-major store that
+    share a keypoint joined into tracks on the device.  Row r owns image / x /
+    y[row_start[r]:row_start[r + 1]].  An observation's keypoint is the
+    smallest observation index with its image and coordinates, a row's
+    component the smallest row index reachable through shared keypoints; a
+    component with two different keypoints of one image is conflicting, and its
+    rows get the label -1 (MERGE_DROP) or their own index (MERGE_KEEP_ROWS).
+    Returns a dict: keypoint (n_obs,) int32, component (n_rows,) int32,
+    conflict (n_rows,) bool, label (n_rows,) int32, track_label (n_tracks,)
+    int32 the distinct labels >= 0 ascending, track_start (n_tracks + 1,) int64,
+    track_obs (track_start[-1],) int32 each track's distinct keypoints ordered
+    by (image, keypoint), obs_slot (n_obs,) int32 the place of each
+    observation's keypoint in track_obs or -1.  The arguments are checked
+    before a device is looked for (SfmCoreError on a violation, with no output
+    of the C call written); no rows, or no observations, returns without one."""
+    rs = np.ascontiguousarray(row_start, dtype=np.int64).reshape(-1)
+    image = np.ascontiguousarray(image, dtype=np.int32).reshape(-1)
+    x, y = _f64(x).reshape(-1), _f64(y).reshape(-1)
+    if len(rs) < 1 or len(x) != len(image) or len(y) != len(image):
+        raise ValueError("merge_tracks: row_start needs n_rows + 1 entries and image, x, y one entry per observation")
+    n_rows, n_obs, n_images, policy = len(rs) - 1, len(image), int(n_images), int(policy)
+    bad = (policy not in (MERGE_DROP, MERGE_KEEP_ROWS) or n_images < 0 or rs[0] != 0 or bool(np.any(np.diff(rs) < 0))
+           or rs[-1] != n_obs or bool(n_obs and (image.min() < 0 or image.max() >= n_images))
+           or not bool(np.isfinite(x).all() and np.isfinite(y).all()))
+    if not bad and n_rows and n_obs:
+        require_device()
+    keypoint, obs_slot, track_obs = (np.full(n_obs, -1, dtype=np.int32) for _ in range(3))
+    component, label, track_label = (np.full(n_rows, -1, dtype=np.int32) for _ in range(3))
+    conflict = np.zeros(n_rows, dtype=np.uint8)
+    track_start = np.zeros(n_rows + 1, dtype=np.int64)
+    n_tracks = np.zeros(1, dtype=np.int64)
+    _check(_lib.sfm_merge_tracks(_p(rs, _i64), n_rows, _p(image, _i32), _p(x), _p(y), n_obs, n_images, policy,
+                                 _p(keypoint, _i32), _p(component, _i32), _p(conflict, _u8), _p(label, _i32),
+                                 _p(n_tracks, _i64), _p(track_label, _i32), _p(track_start, _i64),
+                                 _p(track_obs, _i32), _p(obs_slot, _i32), DEVICE))
+    nt = int(n_tracks[0])
+    track_start = track_start[:nt + 1].copy()
+    return dict(keypoint=keypoint, component=component, conflict=conflict.astype(bool), label=label,
+                track_label=track_label[:nt].copy(), track_start=track_start,
+                track_obs=track_obs[:int(track_start[-1])].copy(), obs_slot=obs_slot)
 
 
 def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,

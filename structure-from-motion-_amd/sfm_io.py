@@ -184,6 +184,46 @@ class MatchStore:
         points_2d = np.column_stack([self.x[keep], self.y[keep]])
         return valid_point_indices, cam.astype(np.int64), point_indices, points_2d
 
+    def merge_tracks(self, conflicts="drop"):
+        """merge_tracks(self, conflicts): the rows that share a keypoint joined into tracks."""
+        return merge_tracks(self, conflicts)
+
+
+def merge_tracks(store, conflicts="drop"):
+    """Join the rows of ``store`` that share a keypoint into tracks, on the
+    device (sfm_merge_tracks).  A matching-file line lists only the direct
+    matches of one keypoint, so one scene point arrives as several rows; a
+    keypoint is an (image, x, y) with equal coordinates, two rows are joined
+    when they contain the same keypoint, and a component that holds two
+    different keypoints of one image is conflicting: its rows are left out
+    (``conflicts="drop"``) or stay the tracks they are (``"keep_rows"``).
+    Returns (merged, row_track, obs_map).  ``merged`` is a new MatchStore,
+    feature-major with images ascending, which every method and stage accepts
+    as it accepts ``store``: its features are the tracks (ascending smallest
+    row), its observations the tracks' distinct keypoints with the
+    representative's coordinates, its flag the OR of the flags of the store's
+    observations that map to it.  ``row_track`` (n_features,) is the merged
+    feature of each row of ``store`` or -1, ``obs_map`` (len(store),) the merged
+    observation of each of its observations or -1, so that per-row results
+    (world points, filtered_world_coords) and per-observation results can be
+    carried across.  ``store`` is not modified.  It comes right after
+    read_matching and before verify_pairs."""
+    policies = {"drop": _core.MERGE_DROP, "keep_rows": _core.MERGE_KEEP_ROWS}
+    if conflicts not in policies:
+        raise ValueError('merge_tracks: conflicts must be "drop" or "keep_rows"')
+    out = _core.merge_tracks(store._row_start, store.image, store.x, store.y, store.n_images, policies[conflicts])
+    track_start, track_obs = out["track_start"], out["track_obs"]
+    n_tracks = len(out["track_label"])
+    feature = np.repeat(np.arange(n_tracks, dtype=np.int32), np.diff(track_start))
+    merged = MatchStore(n_tracks, store.n_images, feature, store.image[track_obs].copy(), store.x[track_obs].copy(),
+                        store.y[track_obs].copy())
+    obs_map = out["obs_slot"].astype(np.int64)
+    kept = obs_map >= 0
+    np.bitwise_or.at(merged.flag, obs_map[kept], store.flag[kept])
+    label = out["label"]
+    row_track = np.where(label >= 0, np.searchsorted(out["track_label"], label), -1).astype(np.int64)
+    return merged, row_track, obs_map
+
 
 def read_matching(data_path, no_of_images, n_threads=0):
     """Parse data_path/matching1..(no_of_images-1).txt into a MatchStore."""

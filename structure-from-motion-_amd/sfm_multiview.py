@@ -19,10 +19,15 @@ of the store in one call (``sfm_verify_pairs``), which sets the flags the others
 read.  ``init_pairs`` follows it: the pose, cheirality, parallax and
 homography support of every verified pair in one call (``sfm_init_pairs``), and
 from them the pair to start the reconstruction from.
+
+``merge_tracks`` comes before every one of them, right after read_matching: the
+store's rows that share a keypoint joined into tracks on the device
+(``sfm_merge_tracks``; sfm_io.merge_tracks, also MatchStore.merge_tracks).
 """
 import numpy as np
 
 import _sfmcore as _core
+from sfm_io import merge_tracks  # noqa: F401  (the stage list's first entry lives with the store)
 from sfm_two_view import projection
 
 
