@@ -686,6 +686,52 @@ int sfm_merge_tracks(const int64_t *row_start, int64_t n_rows, const int32_t *im
                      int device);
 
 /* ---------------------------------------------------------------------
+ * Descriptor matching: image pairs to matches, on the device.  The stage in
+ * front of track merging; the reference ships matching files and nothing
+ * that produces them.
+ * desc is n_kp x dim uint8, row-major (SIFT / RootSIFT descriptors as
+ * extractors store them), dim 64, 128 or 256; image k owns the keypoints
+ * [img_start[k], img_start[k+1]) (n_images + 1 entries).  pairs is P x 2
+ * image numbers (i, j), i != j, in either order; an image may appear in any
+ * number of pairs.
+ * Definitions, from which every output follows; integer work except one fp64
+ * product:
+ *   dsq(a, b): the squared Euclidean distance of two descriptors, exact in
+ *     int32 (dim * 255^2 < 2^24);
+ *   for keypoint a of image i in a pair (i, j), the keypoints of j are ordered
+ *     by (dsq, local index): nn is the first of that order and d1 its dsq, d2
+ *     the dsq of the second; with fewer than two keypoints in j d2 is
+ *     INT32_MAX, with none nn = -1 and d1 = INT32_MAX;
+ *   nn_rev of keypoint b of j: the same first-of-order over the keypoints of i;
+ *   a is matched to nn when nn >= 0, d1 <= max_dsq (INT32_MAX switches the
+ *     test off), d2 == INT32_MAX or (double)d1 < (ratio*ratio) * (double)d2
+ *     (ratio*ratio one fp64 product, the right-hand side another), and, with
+ *     cross_check, nn_rev[nn] == a.
+ * The ratio test applies to the forward direction only, so the matches of
+ * (i, j) and of (j, i) may differ.
+ * Outputs, caller-allocated: match_start (P + 1): pair p owns
+ * [match_start[p], match_start[p+1]) of match_a / match_b (keypoint indices
+ * local to image i / j) and match_dsq, `capacity` entries each, the first
+ * match_start[P] written; a pair's matches are in ascending a, the pairs in
+ * the order given.  capacity must be at least the sum over the pairs of N_i,
+ * or of min(N_i, N_j) with cross_check.  Nullable diagnostics, pair-major,
+ * never downloaded when null: nn, d1, d2 (sum of N_i entries each) and nn_rev
+ * (sum of N_j).
+ * SFM_ERR_ARG, found on the host before a device is looked for, with nothing
+ * written: a null required pointer; dim not 64, 128 or 256; img_start not
+ * starting at 0, decreasing or not ending at n_kp; an image with more than
+ * 2^20 keypoints; a pair image outside [0, n_images) or i == j; ratio outside
+ * (0, 1] or not finite; max_dsq < 0; cross_check not 0 or 1; capacity below
+ * the bound.  P == 0 succeeds without a device.
+ * Every output is the same from run to run (integer minima and a scan).
+ * sfm_last_timings: upload, kernels, download.
+ * ------------------------------------------------------------------- */
+int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const int64_t *img_start, int32_t n_images, int32_t dim,
+                          const int32_t *pairs, int64_t P, double ratio, int32_t max_dsq, int32_t cross_check,
+                          int64_t capacity, int64_t *match_start, int32_t *match_a, int32_t *match_b,
+                          int32_t *match_dsq, int32_t *nn, int32_t *d1, int32_t *d2, int32_t *nn_rev, int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

@@ -116,6 +116,9 @@ SIGNATURES = [
                             _i32, _i32, _d, _i32, _i32, _d, _i32, _d, _u8, _d, _d, _i32, _d, _c]),
     ("sfm_merge_tracks", _c, [_i64, _i, _i32, _d, _d, _i, ctypes.c_int32, ctypes.c_int32, _i32, _i32, _u8, _i32, _i64,
                               _i32, _i64, _i32, _i32, _c]),
+    ("sfm_match_descriptors", _c, [_u8, _i, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _i, ctypes.c_double,
+                                   ctypes.c_int32, ctypes.c_int32, _i, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                   _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -1138,6 +1141,58 @@ def merge_tracks(row_start, image, x, y, n_images, policy=MERGE_DROP):
     return dict(keypoint=keypoint, component=component, conflict=conflict.astype(bool), label=label,
                 track_label=track_label[:nt].copy(), track_start=track_start,
                 track_obs=track_obs[:int(track_start[-1])].copy(), obs_slot=obs_slot)
+
+
+INT32_MAX = 2 ** 31 - 1
+
+
+def match_descriptors(desc, img_start, pairs, ratio=0.8, max_dsq=INT32_MAX, cross_check=True, capacity=None,
+                      want_diagnostics=False):
+    """Descriptor matching (sfm_match_descriptors): for every image pair (i, j)
+    of ``pairs`` (P, 2) the matches of image i's keypoints in image j, on the
+    device.  desc (n_kp, dim) uint8 with dim 64, 128 or 256; image k owns rows
+    img_start[k]:img_start[k + 1].  dsq is the exact integer squared distance;
+    the keypoints of j are ordered by (dsq, index): nn is the first, d1 its dsq,
+    d2 the second's (INT32_MAX without one; nn = -1, d1 = INT32_MAX with no
+    keypoint in j).  a is matched to nn when nn >= 0, d1 <= max_dsq,
+    d2 == INT32_MAX or float(d1) < (ratio * ratio) * float(d2), and, with
+    cross_check, the first of i's keypoints in nn's order is a.  The ratio test
+    is on the forward direction only.  ``capacity`` (default the bound: the sum
+    of N_i, or of min(N_i, N_j) with cross_check) sizes the match arrays.
+    Returns a dict: match_start (P + 1,) int64, a, b, dsq (match_start[-1],)
+    int32 -- pair p owns [match_start[p], match_start[p + 1]), ascending a --
+    and, with want_diagnostics, nn, d1, d2 (sum of N_i,) and nn_rev (sum of
+    N_j,) int32, pair-major.  The arguments are checked before a device is
+    looked for (SfmCoreError, nothing written); P == 0 needs no device."""
+    desc = np.ascontiguousarray(desc, dtype=np.uint8)
+    if desc.ndim != 2:
+        raise ValueError("match_descriptors: desc must be (n_kp, dim)")
+    st = np.ascontiguousarray(img_start, dtype=np.int64).reshape(-1)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if len(st) < 1:
+        raise ValueError("match_descriptors: img_start needs n_images + 1 entries")
+    n_kp, dim = desc.shape
+    n_images, P = len(st) - 1, len(pairs)
+    n = np.diff(st)
+    inside = bool(P == 0 or (pairs.min() >= 0 and pairs.max() < n_images))
+    ni = n[pairs[:, 0]] if inside else np.zeros(0, dtype=np.int64)
+    nj = n[pairs[:, 1]] if inside else np.zeros(0, dtype=np.int64)
+    bound = int(np.minimum(ni, nj).sum() if cross_check else ni.sum())
+    capacity = max(bound, 0) if capacity is None else int(capacity)
+    match_start = np.zeros(P + 1, dtype=np.int64)
+    a, b, dsq = (np.full(max(capacity, 0), -1, dtype=np.int32) for _ in range(3))
+    diag = [None] * 4
+    if want_diagnostics:
+        diag = [np.full(max(int(k.sum()), 0), -1, dtype=np.int32) for k in (ni, ni, ni, nj)]
+    _check(_lib.sfm_match_descriptors(_p(desc, _u8), n_kp, _p(st, _i64), n_images, dim, _p(pairs, _i32), P,
+                                      float(ratio), int(max_dsq), int(bool(cross_check)), capacity,
+                                      _p(match_start, _i64), _p(a, _i32), _p(b, _i32), _p(dsq, _i32),
+                                      *(None if d is None else _p(d, _i32) for d in diag), DEVICE))
+    m = int(match_start[-1])
+    out = dict(match_start=match_start, a=a[:m].copy(), b=b[:m].copy(), dsq=dsq[:m].copy())
+    if want_diagnostics:
+        out.update(nn=diag[0], d1=diag[1], d2=diag[2], nn_rev=diag[3])
+    return out
 
 
 def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,

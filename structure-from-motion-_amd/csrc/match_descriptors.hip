@@ -1,0 +1,430 @@
+// Descriptor matching: for every image pair the nearest and second nearest
+// descriptor of each keypoint, the ratio / distance / cross-check tests and the
+// compacted matches, on the device.  The reference ships matching files and
+// nothing that produces them; this is the stage in front of sfm_merge_tracks.
+//
+// Distances are exact integers (include/sfmcore.h).  The bytes are biased by
+// -128 into signed i8 (one XOR with 0x80; a common shift leaves ||a - b||^2
+// unchanged) and dsq = ||a'||^2 + ||b'||^2 - 2 a'.b' with the products a'.b' on
+// the i8 MFMA (v_mfma_i32_16x16x64_i8) and the norms computed once per call.
+// Every term is below 2^22 in magnitude, so the int32 accumulation is exact.
+//
+//   k_md_norms   ||a'||^2 of every keypoint, 16 bytes per thread.
+//   k_md_nn      a workgroup of 4 waves owns MD_BM = 128 rows of the pair's
+//                first image: each wave keeps the A fragments of its 32 rows in
+//                registers for the whole kernel (lane l: row l & 15, bytes
+//                16 (l >> 4) .. + 15 of each 64-byte k step).  The second
+//                image's descriptors stream through LDS in tiles of MD_TN = 64
+//                columns, double buffered (global -> registers before the
+//                tile's products, registers -> the other buffer after them, one
+//                barrier per tile), rows padded by 16 bytes so that the 16
+//                rows one ds_read_b128 phase touches fall into distinct banks.
+//                A and B use the same (lane, byte) -> k map, so the k order
+//                inside a step cannot matter to the sum.  Of the 16 x 16 result
+//                a lane holds column l & 15 and rows 4 (l >> 4) + 0..3: per
+//                row it keeps the running minimum of w = ||b'||^2 - 2 a'.b'
+//                (||a'||^2 is added at the end), the column of the minimum
+//                and the second smallest w.  Columns arrive ascending, so a
+//                strict < keeps the smaller index on a tie, and the second of
+//                the (dsq, index) order is just the second smallest value:
+//                m2 = med3(m1, m2, w).  The 16 lanes of a row are merged by
+//                the same order at the end.  Columns past the image's end
+//                carry a norm that no real w reaches.
+//                The reverse nearest neighbours (nn_rev) are a second launch
+//                with the pair's images swapped (see DESIGN.md for the
+//                alternative measured).
+//   k_md_accept  the tests of a keypoint; one fp64 product.
+//   rocPRIM      an exclusive scan of the accept flags: each match's place.
+//   k_md_write   match_start and the compacted matches.
+//
+// Integer minima and a scan: every output is the same from run to run.
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "staging.hpp"
+
+namespace sfm {
+
+constexpr int MD_THREADS = 256;
+constexpr int MD_WAVES = 4;
+constexpr int MD_MS = 2;                       // 16-row subtiles per wave
+constexpr int MD_BM = MD_WAVES * MD_MS * 16;   // rows of a workgroup
+constexpr int MD_TN = 64;                      // columns of an LDS tile
+constexpr int MD_PAD = 16;                     // bytes after each LDS row
+constexpr int32_t MD_NONE = INT32_MAX;
+constexpr int32_t MD_OUTSIDE = INT32_MAX - (1 << 24);  // norm of a column past the end: w stays >= 2^30
+constexpr int32_t MD_VALID = 1 << 30;                  // every real w is far below
+constexpr int64_t MD_MAX_KP = (int64_t)1 << 20;
+
+typedef int md_v4i __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int md_sq4(uint32_t v) {  // sum of squares of four signed bytes
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = (int)(int8_t)(v >> (8 * k));
+        s += b * b;
+    }
+    return s;
+}
+
+// norm[kp] = || desc[kp] - 128 ||^2; DIM / 16 threads per keypoint
+template <int DIM>
+__global__ __launch_bounds__(MD_THREADS) void k_md_norms(const uint8_t *desc, int64_t n_kp, int32_t *norm) {
+    constexpr int CH = DIM / 16;
+    const int64_t g = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
+    const int64_t kp = g / CH;
+    int s = 0;
+    if (kp < n_kp) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(desc + g * 16);
+        s = md_sq4(v.x ^ 0x80808080u) + md_sq4(v.y ^ 0x80808080u) + md_sq4(v.z ^ 0x80808080u) +
+            md_sq4(v.w ^ 0x80808080u);
+    }
+#pragma unroll
+    for (int o = 1; o < CH; o <<= 1) s += __shfl_xor(s, o);
+    if (kp < n_kp && g % CH == 0) norm[kp] = s;
+}
+
+// merge the running (m1, i1, m2) of another lane into this one's, by (w, column)
+__device__ __forceinline__ void md_merge(int32_t &m1, int32_t &i1, int32_t &m2, int32_t om1, int32_t oi1, int32_t om2) {
+    const bool other = om1 < m1 || (om1 == m1 && oi1 < i1);
+    const int32_t lo2 = other ? om2 : m2, hi1 = other ? m1 : om1;
+    m2 = lo2 < hi1 ? lo2 : hi1;
+    m1 = other ? om1 : m1;
+    i1 = other ? oi1 : i1;
+}
+
+// pairs is (first, second) per pair when !SWAP and read as (second, first) when
+// SWAP; row_off[p] is where the pair's rows start in nn / d1 / d2.
+template <int DIM, bool SWAP>
+__global__ __launch_bounds__(MD_THREADS) void k_md_nn(const uint8_t *__restrict__ desc, const int32_t *__restrict__ norm,
+                                                      const int64_t *__restrict__ img_start,
+                                                      const int32_t *__restrict__ pairs, int64_t P,
+                                                      const int64_t *__restrict__ row_off, int32_t *__restrict__ nn,
+                                                      int32_t *__restrict__ d1, int32_t *__restrict__ d2) {
+    constexpr int KS = DIM / 64;                          // k steps
+    constexpr int STRIDE = DIM + MD_PAD;                  // bytes of an LDS row
+    constexpr int CH = DIM / 16;                          // 16-byte chunks per row
+    constexpr int NQ = MD_TN * CH / MD_THREADS;           // chunks a thread stages per tile
+    static_assert(MD_TN * CH % MD_THREADS == 0, "a tile is a whole number of passes");
+    __shared__ __attribute__((aligned(16))) uint8_t sB[2][MD_TN * STRIDE];
+    __shared__ int32_t sNb[2][MD_TN];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    for (int64_t p = blockIdx.y; p < P; p += gridDim.y) {
+        const int32_t ii = pairs[2 * p + (SWAP ? 1 : 0)], jj = pairs[2 * p + (SWAP ? 0 : 1)];
+        const int64_t is = img_start[ii], js = img_start[jj];
+        const int32_t ni = (int32_t)(img_start[ii + 1] - is), nj = (int32_t)(img_start[jj + 1] - js);
+        const int32_t row0 = (int32_t)blockIdx.x * MD_BM;
+        if (row0 >= ni) continue;  // uniform over the workgroup
+        const int32_t wrow0 = row0 + wave * (MD_MS * 16);
+
+        // this wave's rows, biased, in registers
+        md_v4i a[MD_MS][KS];
+#pragma unroll
+        for (int ms = 0; ms < MD_MS; ++ms) {
+            const int32_t r = wrow0 + ms * 16 + lr;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                md_v4i v = {0, 0, 0, 0};
+                if (r < ni) {
+                    v = *reinterpret_cast<const md_v4i *>(desc + (is + r) * DIM + ks * 64 + lk * 16);
+                    v ^= (int)0x80808080;
+                }
+                a[ms][ks] = v;
+            }
+        }
+        int32_t m1[MD_MS][4], i1[MD_MS][4], m2[MD_MS][4];
+#pragma unroll
+        for (int ms = 0; ms < MD_MS; ++ms)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                m1[ms][j] = MD_NONE;
+                m2[ms][j] = MD_NONE;
+                i1[ms][j] = -1;
+            }
+
+        const int32_t ntiles = (nj + MD_TN - 1) / MD_TN;
+        md_v4i st[NQ];
+        int32_t st_nb = MD_OUTSIDE;
+        // tile t of the second image: global -> registers, registers -> LDS buffer
+        auto fetch = [&](int32_t t) {
+            const int32_t c0 = t * MD_TN;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int c = tid + q * MD_THREADS, col = c / CH, kc = c % CH;
+                md_v4i v = {0, 0, 0, 0};
+                if (c0 + col < nj) {
+                    v = *reinterpret_cast<const md_v4i *>(desc + (js + c0 + col) * DIM + kc * 16);
+                    v ^= (int)0x80808080;
+                }
+                st[q] = v;
+            }
+            if (tid < MD_TN) st_nb = c0 + tid < nj ? norm[js + c0 + tid] : MD_OUTSIDE;
+        };
+        auto stash = [&](int buf) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int c = tid + q * MD_THREADS, col = c / CH, kc = c % CH;
+                *reinterpret_cast<md_v4i *>(&sB[buf][col * STRIDE + kc * 16]) = st[q];
+            }
+            if (tid < MD_TN) sNb[buf][tid] = st_nb;
+        };
+
+        __syncthreads();  // the previous pair's last tile is no longer read
+        if (ntiles > 0) {
+            fetch(0);
+            stash(0);
+        }
+        __syncthreads();
+        for (int32_t t = 0; t < ntiles; ++t) {
+            const int cur = t & 1;
+            if (t + 1 < ntiles) fetch(t + 1);
+#pragma unroll
+            for (int ns = 0; ns < MD_TN / 16; ++ns) {
+                md_v4i b[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    b[ks] = *reinterpret_cast<const md_v4i *>(&sB[cur][(ns * 16 + lr) * STRIDE + ks * 64 + lk * 16]);
+                const int32_t nb = sNb[cur][ns * 16 + lr];
+                const int32_t col = t * MD_TN + ns * 16 + lr;
+#pragma unroll
+                for (int ms = 0; ms < MD_MS; ++ms) {
+                    md_v4i acc = {0, 0, 0, 0};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks)
+                        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[ms][ks], b[ks], acc, 0, 0, 0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int32_t w = nb - 2 * acc[j];
+                        const int32_t lo = m1[ms][j];
+                        // the second smallest so far: the median of (m1 <= m2, w)
+                        m2[ms][j] = min(m2[ms][j], max(lo, w));
+                        i1[ms][j] = w < lo ? col : i1[ms][j];
+                        m1[ms][j] = min(lo, w);
+                    }
+                }
+            }
+            if (t + 1 < ntiles) stash(cur ^ 1);
+            __syncthreads();
+        }
+
+        // the 16 lanes that share a row (the same lane >> 4), then the row's outputs
+#pragma unroll
+        for (int ms = 0; ms < MD_MS; ++ms)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int32_t x1 = m1[ms][j], xi = i1[ms][j], x2 = m2[ms][j];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) {
+                    const int32_t o1 = __shfl_xor(x1, o), oi = __shfl_xor(xi, o), o2 = __shfl_xor(x2, o);
+                    md_merge(x1, xi, x2, o1, oi, o2);
+                }
+                const int32_t r = wrow0 + ms * 16 + lk * 4 + j;
+                if (lr == 0 && r < ni) {
+                    const int32_t na = norm[is + r];
+                    const bool has1 = x1 < MD_VALID, has2 = x2 < MD_VALID;
+                    const int64_t o = row_off[p] + r;
+                    nn[o] = has1 ? xi : -1;
+                    if (d1) d1[o] = has1 ? na + x1 : MD_NONE;
+                    if (d2) d2[o] = has2 ? na + x2 : MD_NONE;
+                }
+            }
+    }
+}
+
+// flag[row_off[p] + a] = 1 when keypoint a of the pair's first image is matched
+__global__ __launch_bounds__(MD_THREADS) void k_md_accept(const int64_t *img_start, const int32_t *pairs, int64_t P,
+                                                          const int64_t *row_off, const int64_t *col_off,
+                                                          const int32_t *nn, const int32_t *d1, const int32_t *d2,
+                                                          const int32_t *nn_rev, double ratio_sq, int32_t max_dsq,
+                                                          int32_t *flag) {
+    for (int64_t p = blockIdx.y; p < P; p += gridDim.y) {
+        const int32_t ii = pairs[2 * p];
+        const int32_t ni = (int32_t)(img_start[ii + 1] - img_start[ii]);
+        const int32_t a = (int32_t)blockIdx.x * MD_THREADS + threadIdx.x;
+        if (a >= ni) continue;
+        const int64_t o = row_off[p] + a;
+        const int32_t b = nn[o], e1 = d1[o], e2 = d2[o];
+        bool ok = b >= 0 && e1 <= max_dsq;
+        ok = ok && (e2 == MD_NONE || (double)e1 < ratio_sq * (double)e2);
+        ok = ok && (!nn_rev || nn_rev[col_off[p] + b] == a);
+        flag[o] = ok ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(MD_THREADS) void k_md_write(const int64_t *img_start, const int32_t *pairs, int64_t P,
+                                                         const int64_t *row_off, const int32_t *nn, const int32_t *d1,
+                                                         const int32_t *flag, const int64_t *place,
+                                                         int64_t *match_start, int32_t *match_a, int32_t *match_b,
+                                                         int32_t *match_dsq) {
+    for (int64_t p = blockIdx.y; p < P; p += gridDim.y) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            match_start[p] = place[row_off[p]];
+            if (p == P - 1) match_start[P] = place[row_off[P]];
+        }
+        const int32_t ii = pairs[2 * p];
+        const int32_t ni = (int32_t)(img_start[ii + 1] - img_start[ii]);
+        const int32_t a = (int32_t)blockIdx.x * MD_THREADS + threadIdx.x;
+        if (a >= ni) continue;
+        const int64_t o = row_off[p] + a;
+        if (!flag[o]) continue;
+        const int64_t m = place[o];
+        match_a[m] = a;
+        match_b[m] = nn[o];
+        match_dsq[m] = d1[o];
+    }
+}
+
+}  // namespace sfm
+
+using namespace sfm;
+
+extern "C" int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const int64_t *img_start, int32_t n_images,
+                                     int32_t dim, const int32_t *pairs, int64_t P, double ratio, int32_t max_dsq,
+                                     int32_t cross_check, int64_t capacity, int64_t *match_start, int32_t *match_a,
+                                     int32_t *match_b, int32_t *match_dsq, int32_t *nn, int32_t *d1, int32_t *d2,
+                                     int32_t *nn_rev, int device) {
+    SFM_CHECK_ARG(n_kp >= 0 && n_images >= 0 && P >= 0 && capacity >= 0, "n_kp, n_images, P or capacity < 0");
+    SFM_CHECK_ARG(dim == 64 || dim == 128 || dim == 256, "dim is not 64, 128 or 256");
+    SFM_CHECK_ARG(std::isfinite(ratio) && ratio > 0.0 && ratio <= 1.0, "ratio outside (0, 1]");
+    SFM_CHECK_ARG(max_dsq >= 0, "max_dsq < 0");
+    SFM_CHECK_ARG(cross_check == 0 || cross_check == 1, "cross_check is not 0 or 1");
+    SFM_CHECK_ARG(img_start && match_start, "null pointer");
+    SFM_CHECK_ARG(n_kp == 0 || desc, "null pointer");
+    SFM_CHECK_ARG(P == 0 || pairs, "null pointer");
+    SFM_CHECK_ARG(capacity == 0 || (match_a && match_b && match_dsq), "null pointer");
+    SFM_TRY(check_csr(img_start, n_images, n_kp, "img_start", "keypoint", MD_MAX_KP,
+                      "an image with more than 2^20 keypoints"));
+    // the pairs' extents in the pair-major arrays, and the bound on the matches
+    std::vector<int64_t> off(2 * (size_t)(P + 1));
+    int64_t *row_off = off.data(), *col_off = off.data() + (P + 1);
+    int64_t bound = 0, max_i = 0, max_j = 0;
+    row_off[0] = col_off[0] = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+        SFM_CHECK_ARG(i >= 0 && i < n_images && j >= 0 && j < n_images, "a pair image outside [0, n_images)");
+        SFM_CHECK_ARG(i != j, "a pair of an image with itself");
+        const int64_t ni = img_start[i + 1] - img_start[i], nj = img_start[j + 1] - img_start[j];
+        row_off[p + 1] = row_off[p] + ni;
+        col_off[p + 1] = col_off[p] + nj;
+        bound += cross_check && nj < ni ? nj : ni;
+        if (ni > max_i) max_i = ni;
+        if (nj > max_j) max_j = nj;
+    }
+    SFM_CHECK_ARG(capacity >= bound, "capacity below the sum over the pairs of N_i (of min(N_i, N_j) with cross_check)");
+    const double ratio_sq = ratio * ratio;
+
+    match_start[0] = 0;
+    if (P == 0) return 0;
+    const int64_t n_rows = row_off[P], n_cols = col_off[P];
+    const bool reverse = cross_check || nn_rev;
+
+    ThreadCtx *c = thread_ctx(device);
+    if (!c) return SFM_ERR_HIP;
+    hipStream_t s = c->stream;
+    size_t tmp_bytes = 0;
+    SFM_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, (int32_t *)nullptr, (int64_t *)nullptr, (int64_t)0,
+                                    (size_t)n_rows + 1, rocprim::plus<int64_t>(), s));
+
+    Pack in(c->buf[0]), out(c->buf[1]), work(c->buf[2]);
+    const auto i_desc = in.add<uint8_t>(n_kp * dim);
+    const auto i_is = in.add<int64_t>(n_images + 1);
+    const auto i_pairs = in.add<int32_t>(2 * P);
+    const auto i_ro = in.add<int64_t>(P + 1), i_co = in.add<int64_t>(P + 1);
+    const auto o_ms = out.add<int64_t>(P + 1);
+    const auto o_a = out.add<int32_t>(n_rows), o_b = out.add<int32_t>(n_rows), o_dsq = out.add<int32_t>(n_rows);
+    const auto o_nn = out.add<int32_t>(n_rows), o_d1 = out.add<int32_t>(n_rows), o_d2 = out.add<int32_t>(n_rows);
+    const auto o_rev = out.add<int32_t>(reverse ? n_cols : 0);
+    const auto w_norm = work.add<int32_t>(n_kp);
+    const auto w_flag = work.add<int32_t>(n_rows + 1);  // a last 0, so that the scan's last entry is the total
+    const auto w_place = work.add<int64_t>(n_rows + 1);
+    const auto w_tmp = work.add<char>(tmp_bytes);
+    SFM_TRY(in.reserve());
+    SFM_TRY(out.reserve());
+    SFM_TRY(work.reserve());
+
+    CallTimer tm(c);
+    SFM_TRY(tm.mark(s));
+    SFM_TRY(in.upload(i_desc, desc, s));
+    SFM_TRY(in.upload(i_is, img_start, s));
+    SFM_TRY(in.upload(i_pairs, pairs, s));
+    SFM_TRY(in.upload(i_ro, row_off, s));
+    SFM_TRY(in.upload(i_co, col_off, s));
+    SFM_TRY(tm.mark(s));
+
+    const dim3 T(MD_THREADS);
+    const unsigned gy = (unsigned)(P < 65535 ? P : 65535);
+    const uint8_t *d_desc = in.ptr(i_desc);
+    const int64_t *d_is = in.ptr(i_is), *d_ro = in.ptr(i_ro), *d_co = in.ptr(i_co);
+    const int32_t *d_pairs = in.ptr(i_pairs);
+    int32_t *d_norm = work.ptr(w_norm), *d_flag = work.ptr(w_flag);
+    int32_t *d_nn = out.ptr(o_nn), *d_d1 = out.ptr(o_d1), *d_d2 = out.ptr(o_d2);
+    int32_t *d_rev = reverse ? out.ptr(o_rev) : nullptr;
+#define MD_LAUNCH(kernel, grid, ...)                            \
+    do {                                                        \
+        hipLaunchKernelGGL(kernel, grid, T, 0, s, __VA_ARGS__); \
+        SFM_HIP(hipGetLastError());                             \
+    } while (0)
+#define MD_BY_DIM(launch)     \
+    do {                      \
+        if (dim == 64) {      \
+            launch(64);       \
+        } else if (dim == 128) { \
+            launch(128);      \
+        } else {              \
+            launch(256);      \
+        }                     \
+    } while (0)
+    if (n_kp > 0) {
+        const dim3 g_norm((unsigned)ceil_div(n_kp * (dim / 16), MD_THREADS));
+#define MD_NORMS(D) MD_LAUNCH(k_md_norms<D>, g_norm, d_desc, n_kp, d_norm)
+        MD_BY_DIM(MD_NORMS);
+#undef MD_NORMS
+    }
+    if (max_i > 0) {
+        const dim3 g_fwd((unsigned)ceil_div(max_i, MD_BM), gy);
+#define MD_FWD(D) MD_LAUNCH((k_md_nn<D, false>), g_fwd, d_desc, d_norm, d_is, d_pairs, P, d_ro, d_nn, d_d1, d_d2)
+        MD_BY_DIM(MD_FWD);
+#undef MD_FWD
+    }
+    if (reverse && max_j > 0) {
+        const dim3 g_rev((unsigned)ceil_div(max_j, MD_BM), gy);
+#define MD_REV(D)                                                                                    \
+    MD_LAUNCH((k_md_nn<D, true>), g_rev, d_desc, d_norm, d_is, d_pairs, P, d_co, d_rev, (int32_t *)nullptr, \
+              (int32_t *)nullptr)
+        MD_BY_DIM(MD_REV);
+#undef MD_REV
+    }
+    const dim3 g_rows((unsigned)(max_i > 0 ? ceil_div(max_i, MD_THREADS) : 1), gy);
+    SFM_HIP(hipMemsetAsync(d_flag + n_rows, 0, sizeof(int32_t), s));
+    if (max_i > 0)
+        MD_LAUNCH(k_md_accept, g_rows, d_is, d_pairs, P, d_ro, d_co, d_nn, d_d1, d_d2,
+                  cross_check ? (const int32_t *)d_rev : (const int32_t *)nullptr, ratio_sq, max_dsq, d_flag);
+    size_t tb = tmp_bytes;
+    SFM_HIP(rocprim::exclusive_scan(work.ptr(w_tmp), tb, d_flag, work.ptr(w_place), (int64_t)0, (size_t)n_rows + 1,
+                                    rocprim::plus<int64_t>(), s));
+    MD_LAUNCH(k_md_write, g_rows, d_is, d_pairs, P, d_ro, d_nn, d_d1, d_flag, work.ptr(w_place), out.ptr(o_ms),
+              out.ptr(o_a), out.ptr(o_b), out.ptr(o_dsq));
+#undef MD_BY_DIM
+#undef MD_LAUNCH
+    SFM_TRY(tm.mark(s));
+
+    // match_start first: its last entry sizes the other copies
+    SFM_TRY(out.download(match_start, o_ms, s));
+    SFM_HIP(hipStreamSynchronize(s));
+    const size_t total = (size_t)match_start[P];
+    SFM_TRY(out.download(match_a, o_a, 0, total, s));
+    SFM_TRY(out.download(match_b, o_b, 0, total, s));
+    SFM_TRY(out.download(match_dsq, o_dsq, 0, total, s));
+    SFM_TRY(out.download(nn, o_nn, s));
+    SFM_TRY(out.download(d1, o_d1, s));
+    SFM_TRY(out.download(d2, o_d2, s));
+    SFM_TRY(out.download(nn_rev, o_rev, s));
+    SFM_TRY(tm.finish(s));
+    return 0;
+}

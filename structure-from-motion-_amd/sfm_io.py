@@ -225,6 +225,88 @@ def merge_tracks(store, conflicts="drop"):
     return merged, row_track, obs_map
 
 
+def match_store(keypoints, pair_ij, match_start, a, b):
+    """The MatchStore of a list of matches: one feature row per match, in the
+    matches' order, with the two observations (i, keypoints[i][a]) and
+    (j, keypoints[j][b]), images ascending inside the row; read_matching's
+    dtypes, flags zero."""
+    n = len(a)
+    per_pair = np.diff(match_start)
+    i, j = np.repeat(pair_ij[:, 0], per_pair), np.repeat(pair_ij[:, 1], per_pair)
+    image = np.empty((n, 2), dtype=np.int32)
+    kp = np.empty((n, 2), dtype=np.int64)
+    swap = i > j
+    image[:, 0], image[:, 1] = np.where(swap, j, i), np.where(swap, i, j)
+    kp[:, 0], kp[:, 1] = np.where(swap, b, a), np.where(swap, a, b)
+    start = np.concatenate([[0], np.cumsum([len(k) for k in keypoints])]).astype(np.int64)
+    xy = np.concatenate([np.zeros((0, 2))] + [np.asarray(k, dtype=np.float64).reshape(-1, 2) for k in keypoints])
+    xy = xy[(start[image] + kp).reshape(-1)]
+    feature = np.repeat(np.arange(n, dtype=np.int32), 2)
+    return MatchStore(n, len(keypoints), feature, image.reshape(-1), xy[:, 0].copy(), xy[:, 1].copy())
+
+
+def match_descriptors(keypoints, descriptors, pairs=None, ratio=0.8, max_distance=None, cross_check=True):
+    """Match the descriptors of image pairs on the device
+    (sfm_match_descriptors) and return the matches as a MatchStore: the stage
+    in front of merge_tracks, for images that come with keypoints and
+    descriptors of any extractor and not with matching files.
+    ``keypoints[k]`` is (N_k, 2) x, y of image k and ``descriptors[k]``
+    (N_k, dim) uint8 with dim 64, 128 or 256 (SIFT / RootSIFT as extractors and
+    COLMAP store them).  ``pairs`` is (P, 2) image numbers (i, j), i != j, by
+    default every itertools.combinations pair.  Keypoint a of i is matched to
+    its nearest descriptor b of j (exact integer squared distances, ties to
+    the smaller index) when the distance is at most ``max_distance`` (None: no
+    limit), the nearest is closer than ``ratio`` times the second nearest
+    (squared: d1 < ratio^2 d2) and, with ``cross_check``, a is in turn the
+    nearest of b among i's keypoints.  The ratio test is on the direction
+    i -> j only, so (i, j) and (j, i) may differ.
+    Returns (store, pair_ij, match_start, a, b, dsq): pair p owns
+    [match_start[p], match_start[p + 1]) of a, b (keypoint indices local to
+    image i and j, ascending a) and dsq (the squared distance); ``store`` has
+    one feature row per match in that order with the observations
+    (i, keypoints[i][a]) and (j, keypoints[j][b]), images ascending inside the
+    row, read_matching's dtypes and zero flags, so store.merge_tracks() joins
+    the matches into tracks and verify_pairs accepts either store."""
+    import itertools
+    if len(keypoints) != len(descriptors):
+        raise ValueError("match_descriptors: keypoints and descriptors need one entry per image")
+    n_images = len(keypoints)
+    kps, descs = [], []
+    for k in range(n_images):
+        d = np.asarray(descriptors[k])
+        if d.dtype != np.uint8 or d.ndim != 2:
+            raise ValueError("match_descriptors: descriptors[k] must be (N_k, dim) uint8")
+        if descs and d.shape[1] != descs[0].shape[1]:
+            raise ValueError("match_descriptors: the descriptors differ in length")
+        kp = np.asarray(keypoints[k], dtype=np.float64)
+        if kp.shape != (len(d), 2):
+            raise ValueError("match_descriptors: keypoints[k] must be (N_k, 2) with one row per descriptor")
+        if not np.isfinite(kp).all():
+            raise ValueError("match_descriptors: a keypoint coordinate is not finite")
+        kps.append(kp)
+        descs.append(d)
+    if n_images and descs[0].shape[1] not in (64, 128, 256):
+        raise ValueError("match_descriptors: the descriptor length must be 64, 128 or 256")
+    if pairs is None:
+        pairs = list(itertools.combinations(range(n_images), 2))
+    pair_ij = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pair_ij) and (pair_ij.min() < 0 or pair_ij.max() >= n_images or np.any(pair_ij[:, 0] == pair_ij[:, 1])):
+        raise ValueError("match_descriptors: pairs must be (i, j) with i != j in [0, n_images)")
+    if not (np.isfinite(ratio) and 0.0 < ratio <= 1.0):
+        raise ValueError("match_descriptors: ratio must be in (0, 1]")
+    max_dsq = _core.INT32_MAX
+    if max_distance is not None:
+        if not (np.isfinite(max_distance) and max_distance >= 0):
+            raise ValueError("match_descriptors: max_distance must be finite and >= 0")
+        max_dsq = int(min(np.floor(float(max_distance) ** 2), _core.INT32_MAX))
+    dim = descs[0].shape[1] if n_images else 128
+    desc = np.concatenate([np.zeros((0, dim), dtype=np.uint8)] + descs)
+    img_start = np.concatenate([[0], np.cumsum([len(d) for d in descs])]).astype(np.int64)
+    out = _core.match_descriptors(desc, img_start, pair_ij, ratio, max_dsq, cross_check)
+    store = match_store(kps, pair_ij, out["match_start"], out["a"], out["b"])
+    return store, pair_ij, out["match_start"], out["a"], out["b"], out["dsq"]
+
+
 def read_matching(data_path, no_of_images, n_threads=0):
     """Parse data_path/matching1..(no_of_images-1).txt into a MatchStore."""
     nf, feat, img, x, y = _core.parse_matching(data_path, no_of_images, n_threads)

@@ -28,6 +28,7 @@ import numpy as np
 
 import _sfmcore as _core
 from sfm_io import merge_tracks  # noqa: F401  (the stage list's first entry lives with the store)
+from sfm_io import match_descriptors  # noqa: F401  (in front of it: descriptors to a store)
 from sfm_two_view import projection
 
 
