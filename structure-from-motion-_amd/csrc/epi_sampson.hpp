@@ -6,6 +6,7 @@
 // and score assume x2^T F x1 = 0; nothing of that is touched here, these
 // functions stand beside it.
 #pragma once
+#include "hyp_batch.hpp"
 #include "sfm_geom.hpp"
 
 namespace sfm {
@@ -161,6 +162,36 @@ __device__ __forceinline__ bool vp_inlier(const double *F, double x, double y, d
     den = (l0 * l0 + l1 * l1) + (m0 * m0 + m1 * m1);
     e2 = e * e;
     return den > 0.0 && e2 < thr2 * den;
+}
+
+struct EpiPair {
+    const double2 *x1, *x2;  // the pair's first correspondence
+    int n;
+};
+
+// mask[i] = the inlier rule under F for the pair's correspondence i; count and
+// the inliers' squared Sampson distances summed over a workgroup of NT threads
+// (thread t owns i = t, t + NT, ...).  red: NT / 64 x NV, NV >= 2.
+template <int NT, int NV>
+__device__ __forceinline__ void epi_mask(const EpiPair &w, const double *F, double thr2, uint8_t *mask, int &count,
+                                         double &cost, double (*red)[NV]) {
+#pragma clang fp contract(off)
+    double acc[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+    for (int i = threadIdx.x; i < w.n; i += NT) {
+        const double2 p = w.x1[i], q = w.x2[i];
+        double e2, den;
+        const bool in = vp_inlier(F, p.x, p.y, q.x, q.y, thr2, e2, den);
+        mask[i] = in ? 1 : 0;
+        if (in) {
+            acc[0] += 1.0;
+            acc[1] += e2 / den;
+        }
+    }
+    wg_sum<NT / 64, NV>(acc, red);
+    count = (int)acc[0];
+    cost = acc[1];
 }
 
 }  // namespace sfm

@@ -8,16 +8,17 @@
 // Sampson distance in pixels), so F goes straight into sfm_init_pairs.  The
 // reference has no counterpart.
 //
-//   k_ep_fit_score  flat grid over (pair, hypothesis tile) from a host prefix
-//                   table, as k_vp_fit_score.  Fit: one thread per hypothesis,
-//                   four lanes of every wave at a time, the 10 x 20 constraint
-//                   matrix in LDS (five_point.hpp).  Score: the pair's
-//                   correspondences are staged through LDS in tiles of 1024 (the
-//                   fit's workspace, reused), a wave per (hypothesis, solution),
-//                   ballot popcount of the inlier rule and a fixed-order sum of
-//                   the inliers' squared distances; empty solution slots are
-//                   skipped wave-uniformly.  Per hypothesis the best solution
-//                   (count, then cost, then the earliest) is written out.
+// The grid, the block table and the fixed-order sums are the scaffold's
+// (hyp_batch.hpp); k_ep_fit_score keeps the scaffold's device loops written out.
+//
+//   k_ep_fit_score  Fit: one thread per hypothesis, four lanes of every wave at
+//                   a time, the 10 x 20 constraint matrix in LDS
+//                   (five_point.hpp).  Score: tiles of 1024 in the fit's
+//                   workspace, reused; a wave per (hypothesis, solution), the
+//                   inlier rule and a fixed-order sum of the inliers' squared
+//                   distances; empty solution slots are skipped wave-uniformly.
+//                   Per hypothesis the best solution (count, then cost, then
+//                   the earliest) is written out.
 //   k_ep_refit      one workgroup per pair: the winner (count, then cost, then
 //                   the earliest hypothesis), its mask, then rounds of the
 //                   five-parameter fit over the current inliers (per-thread
@@ -25,14 +26,12 @@
 //                   tree, the solve by every thread on the same bits), a re-score
 //                   of the whole pair and the not-worse test.
 //
-// Every sum runs in a fixed order over quantities of the pair alone and counts
-// are integers, so a pair's outputs do not depend on the batch it is in.  No
-// float atomics anywhere.
+// No float atomics anywhere.
 #include <cmath>
 #include <cstring>
 
 #include "five_point.hpp"
-#include "staging.hpp"
+#include "hyp_batch.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,20 +46,10 @@ constexpr int EP_TILE = 1024;                   // correspondences per LDS tile 
 constexpr int EP_SMEM = EP_FIT * EP_WS > 4 * EP_TILE ? EP_FIT * EP_WS : 4 * EP_TILE;  // doubles
 constexpr int EP_RT = 256;                      // refit
 constexpr int EP_RW = EP_RT / 64;
-static_assert(EP_RW == 4, "ep_wg_sum adds four wave results");
 
-// sum over the 64 lanes by a butterfly: both partners add the same pair, so
-// every lane holds the same bits
-__device__ __forceinline__ double ep_wave_sum(double x) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) x += __shfl_xor(x, w);
-    return x;
-}
-
-// blk_start (n_live + 1): the first block of each live pair (n_p >= 5); tab
-// (n_live x 2): the pair and the hypotheses per block chosen for it.  Per
-// hypothesis: n_sol; h_count, h_cost, h_E (9) of its best solution (h_count -1
-// without one).  counts (P x H x 10) and models (P x H x 10 x 9) may be null.
+// Live pairs: n_p >= 5.  Per hypothesis: n_sol; h_count, h_cost, h_E (9) of its
+// best solution (h_count -1 without one).  counts (P x H x 10) and models
+// (P x H x 10 x 9) may be null.
 __global__ void __launch_bounds__(EP_THREADS)
 k_ep_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1,
                const double2 *__restrict__ x2, const int32_t *__restrict__ samples, int32_t H,
@@ -74,7 +63,8 @@ k_ep_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // the live pair of this block: the last j with blk_start[j] <= blockIdx.x
+    // tile_of_block, for_each_tile and wave_count written out here on purpose (the scaffold): keep
+    // this text in step with hyp_batch.hpp
     int lo = 0, hi = n_live - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -139,7 +129,7 @@ k_ep_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict
                     }
                     cnt += __popcll(__ballot(in));
                 }
-                acc = ep_wave_sum(acc);
+                acc = wave_sum(acc);
                 if (lane == 0) {  // this wave alone owns hl
                     sCnt[hl][s] += cnt;
                     sCost[hl][s] += acc;
@@ -173,46 +163,6 @@ k_ep_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict
 }
 
 // ------------------------------------------------------------------ phase 2
-// Fixed-order sum of NV values over the workgroup: the butterfly within a wave,
-// then the four wave results as (0 + 1) + (2 + 3).  red: EP_RW x NV.
-template <int NV>
-__device__ __forceinline__ void ep_wg_sum(double (&x)[NV], double (*red)[NV]) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) x[j] = ep_wave_sum(x[j]);
-    __syncthreads();  // the last use of red is over
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) red[threadIdx.x >> 6][j] = x[j];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NV; ++j) x[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
-}
-
-struct EpPair {
-    const double2 *x1, *x2;  // the pair's first correspondence
-    int n;
-};
-
-// mask[i] = the inlier rule under F for the pair's correspondence i; count and
-// the inliers' squared Sampson distances summed (thread t owns i = t, t + 256, ...)
-__device__ __forceinline__ void ep_mask(const EpPair &w, const double *F, double thr2, uint8_t *mask, int &count,
-                                        double &cost, double (*red)[2]) {
-    double acc[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < w.n; i += EP_RT) {
-        const double2 p = w.x1[i], q = w.x2[i];
-        double e2, den;
-        const bool in = vp_inlier(F, p.x, p.y, q.x, q.y, thr2, e2, den);
-        mask[i] = in ? 1 : 0;
-        if (in) {
-            acc[0] += 1.0;
-            acc[1] += e2 / den;
-        }
-    }
-    ep_wg_sum<2>(acc, red);
-    count = (int)acc[0];
-    cost = acc[1];
-}
-
 // (count, cost, hypothesis): more inliers, then the smaller cost, then the earlier
 __device__ __forceinline__ void ep_merge(int32_t &c1, double &s1, int32_t &h1, int32_t c2, double s2, int32_t h2) {
     if (c2 > c1 || (c2 == c1 && (s2 < s1 || (s2 == s1 && h2 < h1)))) {
@@ -240,7 +190,7 @@ k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
     const int64_t ps = pair_start[p];
     const int n = (int)(pair_start[p + 1] - ps);
     if (n < 5) return;
-    const EpPair w{x1 + ps, x2 + ps, n};
+    const EpiPair w{x1 + ps, x2 + ps, n};
     uint8_t *mask = inlier + ps, *trial = mask2 + ps;
     const double thr2 = thr * thr;
 
@@ -272,7 +222,7 @@ k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
 #pragma unroll
         for (int j = 0; j < 9; ++j) E[j] = h_E[(p * H + bh) * 9 + j];
         ep_F(K, E, F);
-        ep_mask(w, F, thr2, mask, n_inl, cost, red2);
+        epi_mask<EP_RT>(w, F, thr2, mask, n_inl, cost, red2);
         info = -3;
         if (bc >= min_inliers) {
             info = 0;
@@ -289,7 +239,7 @@ k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
                     const double2 q1 = w.x1[i], q2 = w.x2[i];
                     ep_accum(m, q1.x, q1.y, q2.x, q2.y, s);
                 }
-                ep_wg_sum<EP_NV>(s, red);
+                wg_sum<EP_RW, EP_NV>(s, red);
 #pragma unroll
                 for (int j = 0; j < 15; ++j) A[j] = s[j];
 #pragma unroll
@@ -309,15 +259,9 @@ k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
                 ep_cross_mat(t, R, G);
                 vp_unit(G, En);
                 ep_F(K, En, Fn);
-                ep_mask(w, Fn, thr2, trial, n2, cost2, red2);
-                // the refitted state replaces the current one only if it is not worse
-                if (!(n2 > n_inl || (n2 == n_inl && cost2 <= cost))) break;
-                int changed = 0;
-                for (int i = tid; i < n; i += EP_RT) {
-                    changed |= mask[i] != trial[i];
-                    mask[i] = trial[i];
-                }
-                changed = __syncthreads_or(changed);
+                epi_mask<EP_RT>(w, Fn, thr2, trial, n2, cost2, red2);
+                if (!not_worse(n2, cost2, n_inl, cost)) break;
+                const int changed = adopt_trial<EP_RT>(mask, trial, n);
 #pragma unroll
                 for (int j = 0; j < 9; ++j) { E[j] = En[j]; F[j] = Fn[j]; }
                 n_inl = n2;
@@ -358,38 +302,16 @@ extern "C" int sfm_essential_pairs(const double *K, const int64_t *pair_start, i
     SFM_CHECK_ARG(P < (int64_t)0x7fffffff / (H * EP_MAX_SOL), "P x H too large for one call");
     SFM_CHECK_ARG(K && pair_start, "null pointer");
     for (int j = 0; j < 9; ++j) SFM_CHECK_ARG(std::isfinite(K[j]), "K is not finite");
-    // K^-1 by the adjugate
     EpK Ki;
-    {
-        const double c00 = K[4] * K[8] - K[5] * K[7], c01 = K[5] * K[6] - K[3] * K[8], c02 = K[3] * K[7] - K[4] * K[6];
-        const double det = (K[0] * c00 + K[1] * c01) + K[2] * c02;
-        SFM_CHECK_ARG(std::isfinite(det) && det != 0.0, "K is singular");
-        const double adj[9] = {c00, K[2] * K[7] - K[1] * K[8], K[1] * K[5] - K[2] * K[4],
-                               c01, K[0] * K[8] - K[2] * K[6], K[2] * K[3] - K[0] * K[5],
-                               c02, K[1] * K[6] - K[0] * K[7], K[0] * K[4] - K[1] * K[3]};
-        for (int j = 0; j < 9; ++j) {
-            Ki.ki[j] = adj[j] / det;
-            SFM_CHECK_ARG(std::isfinite(Ki.ki[j]), "K has no finite inverse");
-        }
-    }
+    const double det = inv3_adjugate(K, Ki.ki);
+    SFM_CHECK_ARG(std::isfinite(det) && det != 0.0, "K is singular");
+    for (int j = 0; j < 9; ++j) SFM_CHECK_ARG(std::isfinite(Ki.ki[j]), "K has no finite inverse");
     SFM_TRY(check_csr(pair_start, P, n_corr, "pair_start", "correspondence", 0x7fffffff,
                       "a pair has too many correspondences"));
-    int64_t n_live = 0;
-    for (int64_t p = 0; p < P; ++p) n_live += pair_start[p + 1] - pair_start[p] >= 5;
+    const int64_t n_live = count_live(pair_start, P, 5);
     SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
     SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t n = pair_start[p + 1] - pair_start[p];
-        if (n < 5) continue;
-        const int32_t *sp = samples + p * H * 5;
-        for (int64_t h = 0; h < H; ++h) {
-            const int32_t *s = sp + h * 5;
-            for (int a = 0; a < 5; ++a) {
-                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_p)");
-                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
-            }
-        }
-    }
+    SFM_TRY(check_samples(pair_start, P, samples, H, 5, 5, "sample outside [0, n_p)"));
     if (P == 0) return 0;
     SFM_CHECK_ARG(E && F && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
                   "null pointer");
@@ -414,31 +336,15 @@ extern "C" int sfm_essential_pairs(const double *K, const int64_t *pair_start, i
 
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    int rc;
-    // block table: a pair of many correspondences gets fewer hypotheses per
-    // block, so that its score loop is spread over more of them
-    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
-    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
-    int64_t blocks = 0, j = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t n = pair_start[p + 1] - pair_start[p];
-        if (n < 5) continue;
-        const int32_t ht = n >= 4 * EP_TILE ? EP_HT / 4 : (n >= EP_TILE ? EP_HT / 2 : EP_HT);
-        blk[j] = (int32_t)blocks;
-        tab[2 * j] = (int32_t)p;
-        tab[2 * j + 1] = ht;
-        blocks += (H + ht - 1) / ht;
-        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
-        ++j;
-    }
-    blk[n_live] = (int32_t)blocks;
+    TileTable tt;
+    SFM_TRY(tt.build(c->pinned, n_live, pair_start, P, 5, H, EP_HT, EP_TILE));
 
     const size_t PH = (size_t)P * (size_t)H;
     Pack in(c->buf[0]), out(c->buf[1]);
     const auto i_ps = in.add<int64_t>(P + 1);
     const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
     const auto i_s = in.add<int32_t>(5 * PH);
-    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto i_t = in.add<int32_t>(tt.words());  // the block table
     const auto o_E = out.add<double>(9 * P), o_F = out.add<double>(9 * P), o_cost = out.add<double>(P);
     const auto o_info = out.add<int32_t>(P), o_ninl = out.add<int32_t>(P);
     const auto o_hyp = out.add<int32_t>(P), o_bc = out.add<int32_t>(P);
@@ -457,9 +363,9 @@ extern "C" int sfm_essential_pairs(const double *K, const int64_t *pair_start, i
     SFM_TRY(in.upload(i_x1, x1, s));
     SFM_TRY(in.upload(i_x2, x2, s));
     SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(in.upload(i_t, tt.blk, s));
     SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_ep_fit_score, dim3((unsigned)blocks), dim3(EP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
+    hipLaunchKernelGGL(k_ep_fit_score, dim3((unsigned)tt.blocks), dim3(EP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
                        in.ptr(i_x2), in.ptr(i_s), (int32_t)H, in.ptr(i_t), in.ptr(i_t, n_live + 1), (int32_t)n_live,
                        Ki, threshold, out.ptr(o_ns), out.ptr(o_hc), out.ptr(o_hs), out.ptr(o_hE),
                        counts ? out.ptr(o_cnt) : nullptr, models ? out.ptr(o_m) : nullptr);
@@ -471,32 +377,19 @@ extern "C" int sfm_essential_pairs(const double *K, const int64_t *pair_start, i
                        out.ptr(o_hyp), out.ptr(o_bc), out.ptr(o_info), out.ptr(o_mask));
     SFM_HIP(hipGetLastError());
     SFM_TRY(tm.mark(s));
-    // live pairs are copied out one run of consecutive pairs at a time, so that
-    // what the host wrote for the pairs of info -1 stays
-    for (int64_t p0 = 0; p0 < P;) {
-        if (pair_start[p0 + 1] - pair_start[p0] < 5) {
-            ++p0;
-            continue;
-        }
-        int64_t p1 = p0;
-        while (p1 < P && pair_start[p1 + 1] - pair_start[p1] >= 5) ++p1;
-        const size_t np = (size_t)(p1 - p0);
-        SFM_TRY(out.download(E + 9 * p0, o_E, 9 * p0, 9 * np, s));
-        SFM_TRY(out.download(F + 9 * p0, o_F, 9 * p0, 9 * np, s));
-        SFM_TRY(out.download(cost + p0, o_cost, p0, np, s));
-        SFM_TRY(out.download(info + p0, o_info, p0, np, s));
-        SFM_TRY(out.download(n_inliers + p0, o_ninl, p0, np, s));
-        SFM_TRY(out.download(best_hyp + p0, o_hyp, p0, np, s));
-        SFM_TRY(out.download(best_count + p0, o_bc, p0, np, s));
-        const int64_t k0 = pair_start[p0], k1 = pair_start[p1];
-        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
-        if (n_sol) SFM_TRY(out.download(n_sol + p0 * H, o_ns, p0 * H, np * H, s));
-        if (counts)
-            SFM_TRY(out.download(counts + p0 * H * EP_MAX_SOL, o_cnt, p0 * H * EP_MAX_SOL, np * H * EP_MAX_SOL, s));
-        if (models)
-            SFM_TRY(out.download(models + p0 * H * EP_MAX_SOL * 9, o_m, p0 * H * EP_MAX_SOL * 9,
-                                 np * H * EP_MAX_SOL * 9, s));
-        p0 = p1;
-    }
+    const size_t S = (size_t)H * EP_MAX_SOL;
+    SFM_TRY(for_each_live_run(pair_start, P, 5, [&](int64_t p0, int64_t p1, int64_t k0, int64_t k1) -> int {
+        SFM_TRY(out.download_rows(E, o_E, 9, p0, p1, s));
+        SFM_TRY(out.download_rows(F, o_F, 9, p0, p1, s));
+        SFM_TRY(out.download_rows(cost, o_cost, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(info, o_info, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(best_count, o_bc, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
+        SFM_TRY(out.download_rows(n_sol, o_ns, H, p0, p1, s));
+        SFM_TRY(out.download_rows(counts, o_cnt, S, p0, p1, s));
+        return out.download_rows(models, o_m, 9 * S, p0, p1, s);
+    }));
     return tm.finish(s);
 }

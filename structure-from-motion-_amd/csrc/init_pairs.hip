@@ -7,12 +7,11 @@
 // and 2); sfm_two_view_select serves one pair per call from candidates built on
 // the host.  Differs on purpose.
 //
-//   k_ip_homog  flat grid over (pair, hypothesis tile) from a host prefix table,
-//               as k_vp_fit_score.  Fit: a thread per hypothesis (Hartley
-//               normalisation, the 8 x 9 DLT system in registers, its null
-//               vector by the Householder LQ, denormalisation, unit norm).
-//               Score: the pair's correspondences are staged through LDS in
-//               tiles of 1024, a wave per hypothesis, ballot popcount.
+//   k_ip_homog  the scaffold's grid, block table and tile loop (hyp_batch.hpp).
+//               Fit: a thread per hypothesis (Hartley normalisation, the 8 x 9
+//               DLT system in registers, its null vector by the Householder LQ,
+//               denormalisation, unit norm).  Score: a wave per hypothesis, the
+//               transfer error over tiles of 1024.
 //   k_ip_pose   one workgroup per pair.  Thread 0: E = K^T F K, the one-sided
 //               Jacobi of E^T, the four candidates and their projections, all
 //               left in LDS.  Every thread: its correspondences i = t, t + 256,
@@ -30,8 +29,8 @@
 #include <cstring>
 
 #include "epi_sampson.hpp"
+#include "hyp_batch.hpp"
 #include "select.hpp"
-#include "staging.hpp"
 #include "triangulate_point.hpp"
 
 namespace sfm {
@@ -87,9 +86,7 @@ __device__ __forceinline__ bool ip_h_inlier(const double *H, double x, double y,
     return du * du + dv * dv < thr2;
 }
 
-// blk_start (n_live + 1): the first block of each live pair (n_p >= 8); tab
-// (n_live x 2): the pair and the hypotheses per block chosen for it.  models
-// (P x Hh x 9); counts (P x Hh).
+// Live pairs: n_p >= 8.  models (P x Hh x 9); counts (P x Hh).
 __global__ void __launch_bounds__(IP_THREADS)
 k_ip_homog(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1, const double2 *__restrict__ x2,
            const int32_t *__restrict__ samples, int32_t Hh, const int32_t *__restrict__ blk_start,
@@ -100,18 +97,11 @@ k_ip_homog(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
     __shared__ double2 s2[IP_TILE];
     __shared__ int32_t sCnt[IP_HT];
     const int tid = threadIdx.x;
-    // the live pair of this block: the last j with blk_start[j] <= blockIdx.x
-    int lo = 0, hi = n_live - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (blk_start[mid] <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int32_t p = tab[2 * lo], ht = tab[2 * lo + 1];
-    const int32_t hb = ((int32_t)blockIdx.x - blk_start[lo]) * ht;
-    const int nh = min(ht, Hh - hb);
-    const int64_t ps = pair_start[p];
-    const int n = (int)(pair_start[p + 1] - ps);
-    const int64_t row0 = (int64_t)p * Hh + hb;
+    const HypTile t = tile_of_block(blk_start, tab, n_live, Hh);
+    const int nh = t.nh;
+    const int64_t ps = pair_start[t.row];
+    const int n = (int)(pair_start[t.row + 1] - ps);
+    const int64_t row0 = (int64_t)t.row * Hh + t.hb;
 
     // ---- fit: a thread per hypothesis (nh <= IP_HT <= IP_THREADS)
     if (tid < nh) {
@@ -137,31 +127,20 @@ k_ip_homog(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const double thr2 = thr * thr;
-    for (int base = 0; base < n; base += IP_TILE) {
-        const int nt = min(IP_TILE, n - base);
-        for (int i = tid; i < nt; i += IP_THREADS) {
-            s1[i] = x1[ps + base + i];
-            s2[i] = x2[ps + base + i];
-        }
-        __syncthreads();
-        for (int hl = wave; hl < nh; hl += IP_WAVES) {
-            double H[9];
+    for_each_tile<IP_THREADS, IP_TILE>(
+        n, [&](int i, int c) { s1[i] = x1[ps + c], s2[i] = x2[ps + c]; },
+        [&](int nt) {
+            for (int hl = wave; hl < nh; hl += IP_WAVES) {
+                double H[9];
 #pragma unroll
-            for (int j = 0; j < 9; ++j) H[j] = sH[hl][j];
-            int cnt = 0;
-            for (int j = 0; j < nt; j += 64) {
-                const int i = j + lane;
-                bool in = false;
-                if (i < nt) {
+                for (int j = 0; j < 9; ++j) H[j] = sH[hl][j];
+                const int cnt = wave_count(nt, [&](int i) {
                     const double2 q1 = s1[i], q2 = s2[i];
-                    in = ip_h_inlier(H, q1.x, q1.y, q2.x, q2.y, thr2);
-                }
-                cnt += __popcll(__ballot(in));
+                    return ip_h_inlier(H, q1.x, q1.y, q2.x, q2.y, thr2);
+                });
+                if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
             }
-            if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
-        }
-        __syncthreads();
-    }
+        });
     if (tid < nh) counts[row0 + tid] = sCnt[tid];
 }
 
@@ -485,20 +464,9 @@ extern "C" int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_
                       "a pair has too many correspondences"));
     SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
     SFM_CHECK_ARG(P == 0 || F, "null pointer");
-    int64_t n_live = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t n = pair_start[p + 1] - pair_start[p];
-        n_live += n >= 8;
-        if (n < 4) continue;
-        const int32_t *sp = hsamples + p * Hh * 4;
-        for (int64_t h = 0; h < Hh; ++h) {
-            const int32_t *s = sp + h * 4;
-            for (int a = 0; a < 4; ++a) {
-                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_p)");
-                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
-            }
-        }
-    }
+    // a pair's samples are checked from four correspondences on; it is live from eight
+    SFM_TRY(check_samples(pair_start, P, hsamples, Hh, 4, 4, "sample outside [0, n_p)"));
+    const int64_t n_live = count_live(pair_start, P, 8);
     if (P == 0) return 0;
     SFM_CHECK_ARG(R && C && counts && best && n_good && median_angle && h_count && h_best && Hbest && info &&
                       ((X && good && angle) || n_corr == 0),
@@ -531,24 +499,8 @@ extern "C" int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_
 
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    int rc;
-    // block table of the homography kernel: a pair of many correspondences gets
-    // fewer hypotheses per block, so that its score loop is spread over more
-    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
-    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
-    int64_t blocks = 0, j = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t n = pair_start[p + 1] - pair_start[p];
-        if (n < 8) continue;
-        const int32_t ht = n >= 4 * IP_TILE ? IP_HT / 4 : (n >= IP_TILE ? IP_HT / 2 : IP_HT);
-        blk[j] = (int32_t)blocks;
-        tab[2 * j] = (int32_t)p;
-        tab[2 * j + 1] = ht;
-        blocks += (Hh + ht - 1) / ht;
-        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
-        ++j;
-    }
-    blk[n_live] = (int32_t)blocks;
+    TileTable tt;  // of the homography kernel
+    SFM_TRY(tt.build(c->pinned, n_live, pair_start, P, 8, Hh, IP_HT, IP_TILE));
 
     const size_t PH = (size_t)P * (size_t)Hh;
     Pack in(c->buf[0]), out(c->buf[1]);
@@ -556,7 +508,7 @@ extern "C" int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_
     const auto i_ps = in.add<int64_t>(P + 1);
     const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
     const auto i_s = in.add<int32_t>(4 * PH);
-    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto i_t = in.add<int32_t>(tt.words());  // the block table
     const auto o_R = out.add<double>(9 * P), o_C = out.add<double>(3 * P), o_med = out.add<double>(P);
     const auto o_Hb = out.add<double>(9 * P), o_cands = out.add<double>(48 * P);
     const auto o_cnt = out.add<int64_t>(4 * P);
@@ -577,10 +529,10 @@ extern "C" int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_
     SFM_TRY(in.upload(i_x1, x1, s));
     SFM_TRY(in.upload(i_x2, x2, s));
     SFM_TRY(in.upload(i_s, hsamples, s));
-    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(in.upload(i_t, tt.blk, s));
     SFM_TRY(tm.mark(s));
     if (Hh > 0) {
-        hipLaunchKernelGGL(k_ip_homog, dim3((unsigned)blocks), dim3(IP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
+        hipLaunchKernelGGL(k_ip_homog, dim3((unsigned)tt.blocks), dim3(IP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
                            in.ptr(i_x2), in.ptr(i_s), (int32_t)Hh, in.ptr(i_t), in.ptr(i_t, n_live + 1),
                            (int32_t)n_live, h_threshold, out.ptr(o_hm), out.ptr(o_hcnt));
         SFM_HIP(hipGetLastError());
@@ -593,34 +545,23 @@ extern "C" int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_
                        in.ptr(i_x2), in.ptr(i_F), (int32_t)Hh, out.ptr(o_hcnt), out.ptr(o_hm), max_reproj, o);
     SFM_HIP(hipGetLastError());
     SFM_TRY(tm.mark(s));
-    // live pairs are copied out one run of consecutive pairs at a time, so that
-    // what the host wrote for the pairs of info -1 stays
-    for (int64_t p0 = 0; p0 < P;) {
-        if (pair_start[p0 + 1] - pair_start[p0] < 8) {
-            ++p0;
-            continue;
-        }
-        int64_t p1 = p0;
-        while (p1 < P && pair_start[p1 + 1] - pair_start[p1] >= 8) ++p1;
-        const size_t np = (size_t)(p1 - p0);
-        SFM_TRY(out.download(R + 9 * p0, o_R, 9 * p0, 9 * np, s));
-        SFM_TRY(out.download(C + 3 * p0, o_C, 3 * p0, 3 * np, s));
-        SFM_TRY(out.download(counts + 4 * p0, o_cnt, 4 * p0, 4 * np, s));
-        SFM_TRY(out.download(best + p0, o_best, p0, np, s));
-        SFM_TRY(out.download(n_good + p0, o_ng, p0, np, s));
-        SFM_TRY(out.download(median_angle + p0, o_med, p0, np, s));
-        SFM_TRY(out.download(h_count + p0, o_hc, p0, np, s));
-        SFM_TRY(out.download(h_best + p0, o_hb, p0, np, s));
-        SFM_TRY(out.download(Hbest + 9 * p0, o_Hb, 9 * p0, 9 * np, s));
-        SFM_TRY(out.download(info + p0, o_info, p0, np, s));
-        const int64_t k0 = pair_start[p0], k1 = pair_start[p1];
-        SFM_TRY(out.download(X + 3 * k0, o_X, 3 * k0, 3 * (k1 - k0), s));
-        SFM_TRY(out.download(good + k0, o_good, k0, k1 - k0, s));
-        SFM_TRY(out.download(angle + k0, o_ang, k0, k1 - k0, s));
-        if (cands) SFM_TRY(out.download(cands + 48 * p0, o_cands, 48 * p0, 48 * np, s));
-        if (Hh > 0 && hcounts) SFM_TRY(out.download(hcounts + p0 * Hh, o_hcnt, p0 * Hh, np * Hh, s));
-        if (Hh > 0 && hmodels) SFM_TRY(out.download(hmodels + p0 * Hh * 9, o_hm, p0 * Hh * 9, np * Hh * 9, s));
-        p0 = p1;
-    }
+    SFM_TRY(for_each_live_run(pair_start, P, 8, [&](int64_t p0, int64_t p1, int64_t k0, int64_t k1) -> int {
+        SFM_TRY(out.download_rows(R, o_R, 9, p0, p1, s));
+        SFM_TRY(out.download_rows(C, o_C, 3, p0, p1, s));
+        SFM_TRY(out.download_rows(counts, o_cnt, 4, p0, p1, s));
+        SFM_TRY(out.download_rows(best, o_best, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(n_good, o_ng, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(median_angle, o_med, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(h_count, o_hc, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(h_best, o_hb, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(Hbest, o_Hb, 9, p0, p1, s));
+        SFM_TRY(out.download_rows(info, o_info, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(X, o_X, 3, k0, k1, s));
+        SFM_TRY(out.download_rows(good, o_good, 1, k0, k1, s));
+        SFM_TRY(out.download_rows(angle, o_ang, 1, k0, k1, s));
+        SFM_TRY(out.download_rows(cands, o_cands, 48, p0, p1, s));
+        SFM_TRY(out.download_rows(hcounts, o_hcnt, Hh, p0, p1, s));
+        return out.download_rows(hmodels, o_hm, 9 * Hh, p0, p1, s);
+    }));
     return tm.finish(s);
 }

@@ -7,15 +7,15 @@
 // four-dimensional null space), and no serial Jacobi.  The reference has no
 // counterpart.
 //
-//   k_p3p_fit_score  flat grid over (view, hypothesis tile) from a host prefix
-//                    table, as k_reg_fit_score.  Solve: one lane per
-//                    hypothesis, all of it in registers, no LDS and no
-//                    shuffles; the poses go to LDS and global memory as they
-//                    are found.  One thread then lists the slots that hold a
-//                    solution.  Score: the view's correspondences are staged
-//                    through LDS in tiles of 1024, a wave per listed slot,
-//                    ballot popcount of the inlier rule (rv_inlier: the fp64
-//                    band prefilter, rv_exact inside the band).  A hypothesis
+// The grid, the block table, the tile loop and the fixed-order sums are the
+// scaffold's (hyp_batch.hpp).
+//
+//   k_p3p_fit_score  Solve: one lane per hypothesis, all of it in registers, no
+//                    LDS and no shuffles; the poses go to LDS and global memory
+//                    as they are found.  One thread then lists the slots that
+//                    hold a solution.  Score: a wave per listed slot, the
+//                    inlier rule over tiles of 1024 (rv_inlier: the fp64 band
+//                    prefilter, rv_exact inside the band).  A hypothesis
 //                    without solutions is never listed.
 //   k_p3p_refine     one workgroup per view: the winner over (hypothesis,
 //                    solution) -- most inliers, then the smaller sum of the
@@ -23,16 +23,13 @@
 //                    register_refine.hpp's refit from its pose.  The sums of
 //                    the tie-break are rv_mask's, one pass over the view per
 //                    slot that ties on the count.
-//
-// Every sum runs in a fixed order over quantities of the view alone, so a
-// view's outputs do not depend on the batch it is in.
 #include <cmath>
 #include <cstring>
 
+#include "hyp_batch.hpp"
 #include "p3p.hpp"
 #include "register_refine.hpp"
 #include "select.hpp"
-#include "staging.hpp"
 
 #pragma clang fp contract(off)
 
@@ -41,9 +38,7 @@ namespace sfm {
 constexpr int P3_HT = 32;               // most hypotheses per workgroup
 constexpr int P3_SLOTS = P3_HT * P3P_MAX_SOL;
 
-// blk_start (n_live + 1): the first block of each live view (n_v >= 4);
-// tab (n_live x 2): the view and the hypotheses per block chosen for it.
-// Per slot (V x H x 4): modelsP the projection (zeros past n_sol), modelsCR
+// Live views: n_v >= 4.  Per slot (V x H x 4): modelsP the projection (zeros past n_sol), modelsCR
 // its C | R (written up to n_sol only), counts (0 past n_sol); n_sol (V x H).
 __global__ void __launch_bounds__(RV_THREADS)
 k_p3p_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_start,
@@ -56,18 +51,11 @@ k_p3p_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_
     __shared__ double2 sxy[RV_TILE];
     __shared__ int32_t sNs[P3_HT], sCnt[P3_SLOTS], sList[P3_SLOTS], sLive;
     const int tid = threadIdx.x;
-    // the live view of this block: the last j with blk_start[j] <= blockIdx.x
-    int lo = 0, hi = n_live - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (blk_start[mid] <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int32_t v = tab[2 * lo], ht = tab[2 * lo + 1];
-    const int32_t hb = ((int32_t)blockIdx.x - blk_start[lo]) * ht;
-    const int nh = min(ht, H - hb);
-    const int64_t vs = view_start[v];
-    const int n = (int)(view_start[v + 1] - vs);
-    const int64_t row0 = (int64_t)v * H + hb;
+    const HypTile t = tile_of_block(blk_start, tab, n_live, H);
+    const int nh = t.nh;
+    const int64_t vs = view_start[t.row];
+    const int n = (int)(view_start[t.row + 1] - vs);
+    const int64_t row0 = (int64_t)t.row * H + t.hb;
 
     // ---- solve: one lane per hypothesis
     if (tid < P3_SLOTS) sCnt[tid] = 0;
@@ -122,36 +110,21 @@ k_p3p_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int live = sLive;
     const double thr2 = thr * thr;
-    for (int base = 0; base < n; base += RV_TILE) {
-        const int nt = min(RV_TILE, n - base);
-        for (int i = tid; i < nt; i += RV_THREADS) {
-            const int64_t c = vs + base + i;
-            const int64_t pi = pt_idx[c];
-            sX[3 * i] = Xg[3 * pi];
-            sX[3 * i + 1] = Xg[3 * pi + 1];
-            sX[3 * i + 2] = Xg[3 * pi + 2];
-            sxy[i] = xy[c];
-        }
-        __syncthreads();
-        for (int s = wave; s < live; s += RV_WAVES) {
-            const int m = sList[s];
-            double P[12];
+    for_each_tile<RV_THREADS, RV_TILE>(
+        n, [&](int i, int c) { rv_stage(Xg, pt_idx, xy, vs + c, sX, sxy, i); },
+        [&](int nt) {
+            for (int s = wave; s < live; s += RV_WAVES) {
+                const int m = sList[s];
+                double P[12];
 #pragma unroll
-            for (int j = 0; j < 12; ++j) P[j] = sP[m][j];
-            int cnt = 0;
-            for (int j = 0; j < nt; j += 64) {
-                const int i = j + lane;
-                bool in = false;
-                if (i < nt) {
+                for (int j = 0; j < 12; ++j) P[j] = sP[m][j];
+                const int cnt = wave_count(nt, [&](int i) {
                     const double2 q = sxy[i];
-                    in = rv_inlier(P, sX[3 * i], sX[3 * i + 1], sX[3 * i + 2], q.x, q.y, thr, thr2);
-                }
-                cnt += __popcll(__ballot(in));
+                    return rv_inlier(P, sX[3 * i], sX[3 * i + 1], sX[3 * i + 2], q.x, q.y, thr, thr2);
+                });
+                if (lane == 0) sCnt[m] += cnt;  // this wave alone owns list entry s
             }
-            if (lane == 0) sCnt[m] += cnt;  // this wave alone owns list entry s
-        }
-        __syncthreads();
-    }
+        });
     if (tid < nh * P3P_MAX_SOL) counts[row0 * P3P_MAX_SOL + tid] = sCnt[tid];
 }
 
@@ -253,22 +226,6 @@ k_p3p_refine(const double *__restrict__ Xg, const int64_t *__restrict__ view_sta
     }
 }
 
-// K^-1 by the adjugate; a singular K gives bearings that are not finite, and
-// with them hypotheses without solutions
-static void invert3(const double *K, double *Ki) {
-    const double c0 = K[4] * K[8] - K[5] * K[7], c1 = K[5] * K[6] - K[3] * K[8], c2 = K[3] * K[7] - K[4] * K[6];
-    const double det = (K[0] * c0 + K[1] * c1) + K[2] * c2;
-    Ki[0] = c0 / det;
-    Ki[1] = (K[2] * K[7] - K[1] * K[8]) / det;
-    Ki[2] = (K[1] * K[5] - K[2] * K[4]) / det;
-    Ki[3] = c1 / det;
-    Ki[4] = (K[0] * K[8] - K[2] * K[6]) / det;
-    Ki[5] = (K[2] * K[3] - K[0] * K[5]) / det;
-    Ki[6] = c2 / det;
-    Ki[7] = (K[1] * K[6] - K[0] * K[7]) / det;
-    Ki[8] = (K[0] * K[4] - K[1] * K[3]) / det;
-}
-
 }  // namespace sfm
 
 using namespace sfm;
@@ -290,23 +247,11 @@ extern "C" int sfm_register_views_p3p(const double *K, const double *X, int64_t 
     SFM_CHECK_ARG(view_start && K, "null pointer");
     SFM_TRY(check_csr(view_start, V, n_corr, "view_start", "correspondence", 0x7fffffff,
                       "a view has too many correspondences"));
-    int64_t n_live = 0;
-    for (int64_t v = 0; v < V; ++v) n_live += view_start[v + 1] - view_start[v] >= 4;
+    const int64_t n_live = count_live(view_start, V, 4);
     SFM_CHECK_ARG(n_corr == 0 || (pt_idx && xy && X), "null pointer");
     SFM_TRY(check_index(pt_idx, n_corr, n_pts, "point index outside [0, n_pts)"));
     SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    for (int64_t v = 0; v < V; ++v) {
-        const int64_t n = view_start[v + 1] - view_start[v];
-        if (n < 4) continue;
-        const int32_t *sv = samples + v * H * 3;
-        for (int64_t h = 0; h < H; ++h) {
-            const int32_t *s = sv + h * 3;
-            for (int a = 0; a < 3; ++a) {
-                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_v)");
-                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
-            }
-        }
-    }
+    SFM_TRY(check_samples(view_start, V, samples, H, 3, 4, "sample outside [0, n_v)"));
     if (V == 0) return 0;
     SFM_CHECK_ARG(C && R && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
                   "null pointer");
@@ -329,25 +274,10 @@ extern "C" int sfm_register_views_p3p(const double *K, const double *X, int64_t 
 
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    int rc;
-    // block table: every hypothesis brings up to four models, so a block takes
-    // a quarter to a half of the hypotheses k_reg_fit_score gives it, and fewer
-    // for a view of many correspondences
-    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
-    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
-    int64_t blocks = 0, j = 0;
-    for (int64_t v = 0; v < V; ++v) {
-        const int64_t n = view_start[v + 1] - view_start[v];
-        if (n < 4) continue;
-        const int32_t ht = n >= 4 * RV_TILE ? P3_HT / 4 : (n >= RV_TILE ? P3_HT / 2 : P3_HT);
-        blk[j] = (int32_t)blocks;
-        tab[2 * j] = (int32_t)v;
-        tab[2 * j + 1] = ht;
-        blocks += (H + ht - 1) / ht;
-        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
-        ++j;
-    }
-    blk[n_live] = (int32_t)blocks;
+    // every hypothesis brings up to four models, so a block takes a quarter to a
+    // half of the hypotheses k_reg_fit_score gives it
+    TileTable tt;
+    SFM_TRY(tt.build(c->pinned, n_live, view_start, V, 4, H, P3_HT, RV_TILE));
 
     const size_t VH = (size_t)V * (size_t)H;
     Pack in(c->buf[0]), out(c->buf[1]);
@@ -355,7 +285,7 @@ extern "C" int sfm_register_views_p3p(const double *K, const double *X, int64_t 
     const auto i_xy = in.add<double2>(n_corr);
     const auto i_X = in.add<double>(3 * n_pts);
     const auto i_pt = in.add<int32_t>(n_corr), i_s = in.add<int32_t>(3 * VH);
-    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto i_t = in.add<int32_t>(tt.words());  // the block table
     const auto o_C = out.add<double>(3 * V), o_R = out.add<double>(9 * V), o_cost = out.add<double>(V);
     const auto o_info = out.add<int32_t>(V), o_ninl = out.add<int32_t>(V);
     const auto o_hyp = out.add<int32_t>(V), o_bc = out.add<int32_t>(V), o_ns = out.add<int32_t>(VH);
@@ -366,7 +296,8 @@ extern "C" int sfm_register_views_p3p(const double *K, const double *X, int64_t 
     SFM_TRY(out.reserve());
     Cam3 cam, cam_inv;
     std::memcpy(cam.k, K, sizeof cam.k);
-    invert3(K, cam_inv.k);
+    // a singular K gives bearings that are not finite, and with them hypotheses without solutions
+    (void)inv3_adjugate(K, cam_inv.k);
     hipStream_t s = c->stream;
     CallTimer tm(c);
     SFM_TRY(tm.mark(s));
@@ -375,9 +306,9 @@ extern "C" int sfm_register_views_p3p(const double *K, const double *X, int64_t 
     SFM_TRY(in.upload(i_X, X, s));
     SFM_TRY(in.upload(i_pt, pt_idx, s));
     SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(in.upload(i_t, tt.blk, s));
     SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_p3p_fit_score, dim3((unsigned)blocks), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
+    hipLaunchKernelGGL(k_p3p_fit_score, dim3((unsigned)tt.blocks), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
                        in.ptr(i_pt), in.ptr(i_xy), in.ptr(i_s), (int32_t)H, cam, cam_inv, in.ptr(i_t),
                        in.ptr(i_t, n_live + 1), (int32_t)n_live, threshold, out.ptr(o_mP), out.ptr(o_mCR),
                        out.ptr(o_cnt), out.ptr(o_ns));
@@ -390,29 +321,18 @@ extern "C" int sfm_register_views_p3p(const double *K, const double *X, int64_t 
                        out.ptr(o_info), out.ptr(o_mask));
     SFM_HIP(hipGetLastError());
     SFM_TRY(tm.mark(s));
-    // live views are copied out one run of consecutive views at a time, so that
-    // what the host wrote for the views of info -1 stays
-    for (int64_t v0 = 0; v0 < V;) {
-        if (view_start[v0 + 1] - view_start[v0] < 4) {
-            ++v0;
-            continue;
-        }
-        int64_t v1 = v0;
-        while (v1 < V && view_start[v1 + 1] - view_start[v1] >= 4) ++v1;
-        const size_t nv = (size_t)(v1 - v0);
-        SFM_TRY(out.download(C + 3 * v0, o_C, 3 * v0, 3 * nv, s));
-        SFM_TRY(out.download(R + 9 * v0, o_R, 9 * v0, 9 * nv, s));
-        SFM_TRY(out.download(cost + v0, o_cost, v0, nv, s));
-        SFM_TRY(out.download(info + v0, o_info, v0, nv, s));
-        SFM_TRY(out.download(n_inliers + v0, o_ninl, v0, nv, s));
-        SFM_TRY(out.download(best_hyp + v0, o_hyp, v0, nv, s));
-        SFM_TRY(out.download(best_count + v0, o_bc, v0, nv, s));
-        const int64_t k0 = view_start[v0], k1 = view_start[v1];
-        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
-        if (n_sol) SFM_TRY(out.download(n_sol + v0 * H, o_ns, v0 * H, nv * H, s));
-        if (counts) SFM_TRY(out.download(counts + v0 * H * NS, o_cnt, v0 * H * NS, nv * H * NS, s));
-        if (models) SFM_TRY(out.download(models + v0 * H * NS * 12, o_mP, v0 * H * NS * 12, nv * H * NS * 12, s));
-        v0 = v1;
-    }
+    SFM_TRY(for_each_live_run(view_start, V, 4, [&](int64_t v0, int64_t v1, int64_t k0, int64_t k1) -> int {
+        SFM_TRY(out.download_rows(C, o_C, 3, v0, v1, s));
+        SFM_TRY(out.download_rows(R, o_R, 9, v0, v1, s));
+        SFM_TRY(out.download_rows(cost, o_cost, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(info, o_info, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(best_count, o_bc, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
+        SFM_TRY(out.download_rows(n_sol, o_ns, H, v0, v1, s));
+        SFM_TRY(out.download_rows(counts, o_cnt, H * NS, v0, v1, s));
+        return out.download_rows(models, o_mP, 12 * H * NS, v0, v1, s);
+    }));
     return tm.finish(s);
 }

@@ -1,17 +1,13 @@
 // What the two view-registration entry points share (register_views.hip:
 // 6-point DLT hypotheses; register_p3p.hip: calibrated 3-point hypotheses):
-// the inlier rule and its division-free prefilter, the fixed-order workgroup
-// sums, and the refit of a winning pose -- rounds of Levenberg-Marquardt on
-// the 6 pose parameters over the current inliers, a re-score of the whole
-// view and the not-worse test.
-//
-// Every sum runs in a fixed order over quantities of the view alone (strided
-// per-thread partial sums, a 64-lane butterfly, four wave results added as
-// (0 + 1) + (2 + 3)); counts are integers.  A view's outputs therefore do not
-// depend on the batch it is in.
+// the inlier rule and its division-free prefilter, and the refit of a winning
+// pose -- rounds of Levenberg-Marquardt on the 6 pose parameters over the
+// current inliers, a re-score of the whole view and the not-worse test.  The
+// fixed-order sums are the scaffold's (hyp_batch.hpp).
 #pragma once
 #include <cmath>
 
+#include "hyp_batch.hpp"
 #include "lm_small.hpp"
 #include "pnp_model.hpp"
 #include "sfm_geom.hpp"
@@ -65,22 +61,14 @@ __device__ __forceinline__ bool rv_inlier(const double *P, double X, double Y, d
     return rv_exact(h0, h1, h2, u, v, thr2, e2);
 }
 
-// Fixed-order sum of NV values over the workgroup: a 64-lane butterfly (both
-// partners add the same pair, so every lane holds the same bits), then the
-// four wave results as (0 + 1) + (2 + 3).  red: RV_WAVES x NV.
-template <int NV>
-__device__ __forceinline__ void rv_wg_sum(double (&x)[NV], double (*red)[NV]) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) x[j] += __shfl_xor(x[j], w);
-    __syncthreads();  // the last use of red is over
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) red[threadIdx.x >> 6][j] = x[j];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NV; ++j) x[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+// correspondence c (an index into pt_idx / xy) to place i of the score loop's LDS tile
+__device__ __forceinline__ void rv_stage(const double *__restrict__ Xg, const int32_t *__restrict__ pt_idx,
+                                         const double2 *__restrict__ xy, int64_t c, double *sX, double2 *sxy, int i) {
+    const int64_t pi = pt_idx[c];
+    sX[3 * i] = Xg[3 * pi];
+    sX[3 * i + 1] = Xg[3 * pi + 1];
+    sX[3 * i + 2] = Xg[3 * pi + 2];
+    sxy[i] = xy[c];
 }
 
 struct RvView {
@@ -107,7 +95,7 @@ __device__ __forceinline__ void rv_mask(const RvView &w, const double *P, double
             acc[1] += e2;
         }
     }
-    rv_wg_sum<2>(acc, red);
+    wg_sum<RV_WAVES, 2>(acc, red);
     count = (int)acc[0];
     cost = acc[1];
 }
@@ -162,7 +150,7 @@ __device__ __forceinline__ void rv_eval(const RvView &w, const Cam3 &K, const do
 #pragma unroll
             for (int b = a; b < 6; ++b) s[u++] += ju[a] * ju[b] + jv[a] * jv[b];
     }
-    rv_wg_sum<RV_NV>(s, red);
+    wg_sum<RV_WAVES, RV_NV>(s, red);
 #pragma unroll
     for (int j = 0; j < 21; ++j) A[j] = s[j];
 #pragma unroll
@@ -311,7 +299,6 @@ __device__ __forceinline__ int rv_refit(const RvView &w, const Cam3 &K, const do
                                         int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev, double (&R)[9],
                                         double (&C)[3], double &cost, int &n_inl, uint8_t *mask, uint8_t *trial,
                                         double (*red)[RV_NV], double (*red2)[2]) {
-    const int tid = threadIdx.x;
     rv_mask(w, P, thr2, mask, n_inl, cost, red2);
     int info = -3;
     if (bc >= min_inliers) {
@@ -328,14 +315,8 @@ __device__ __forceinline__ int rv_refit(const RvView &w, const Cam3 &K, const do
             int n2;
             pnp_projection(K, Cn, Rn, Pn);
             rv_mask(w, Pn, thr2, trial, n2, cost2, red2);
-            // the refitted state replaces the current one only if it is not worse
-            if (!(n2 > n_inl || (n2 == n_inl && cost2 <= cost))) break;
-            int changed = 0;
-            for (int i = tid; i < w.n; i += RV_THREADS) {
-                changed |= mask[i] != trial[i];
-                mask[i] = trial[i];
-            }
-            changed = __syncthreads_or(changed);
+            if (!not_worse(n2, cost2, n_inl, cost)) break;
+            const int changed = adopt_trial<RV_THREADS>(mask, trial, w.n);
 #pragma unroll
             for (int j = 0; j < 9; ++j) R[j] = Rn[j];
 #pragma unroll

@@ -7,15 +7,16 @@
 // is whatever null vector LAPACK returns); six points give 12 equations for the
 // 11 degrees of freedom of P, a determined model.  Differs on purpose.
 //
-//   k_reg_fit_score  flat grid over (view, hypothesis tile) from a host prefix
-//                    table.  Fit: a hypothesis belongs to 16 lanes, lane k < 12
-//                    holding row k of the 12 x 12 DLT system and row k of V;
-//                    one-sided Jacobi rotates column pairs (the three column
-//                    sums are 16-lane butterflies), the column of smallest
-//                    norm names the null vector, rv_post / pnp_projection
-//                    finish the model.  Score: the view's correspondences are
-//                    staged through LDS in tiles of 1024, a wave per hypothesis,
-//                    ballot popcount of the inlier rule.
+// The grid, the block table, the tile loop and the fixed-order sums are the
+// scaffold's (hyp_batch.hpp).
+//
+//   k_reg_fit_score  Fit: a hypothesis belongs to 16 lanes, lane k < 12 holding
+//                    row k of the 12 x 12 DLT system and row k of V; one-sided
+//                    Jacobi rotates column pairs (the three column sums are
+//                    16-lane butterflies), the column of smallest norm names
+//                    the null vector, rv_post / pnp_projection finish the
+//                    model.  Score: a wave per hypothesis, the inlier rule over
+//                    tiles of 1024.
 //   k_reg_refine     one workgroup per view: winner (most inliers, then the
 //                    earliest), its mask, then rounds of Levenberg-Marquardt on
 //                    the 6 pose parameters over the current inliers, a re-score
@@ -26,8 +27,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "hyp_batch.hpp"
 #include "register_refine.hpp"
-#include "staging.hpp"
 #include "select.hpp"
 
 #pragma clang fp contract(off)
@@ -37,6 +38,7 @@ namespace sfm {
 constexpr int RV_GROUP = 16;                       // lanes per hypothesis in the fit
 constexpr int RV_FIT = RV_THREADS / RV_GROUP;      // hypotheses fitted per pass
 constexpr int RV_HT = 64;                          // most hypotheses per workgroup
+static_assert(RV_HT == 4 * RV_FIT, "a block of a long view takes one fit pass, RV_HT / 4");
 constexpr int RV_SWEEPS = 60;
 
 __device__ __forceinline__ double rv_group_sum(double x) {
@@ -137,9 +139,7 @@ __device__ __forceinline__ void rv_post(const double (&p)[12], double (&C)[3], d
     }
 }
 
-// blk_start (n_live + 1): the first block of each live view (n_v >= 6);
-// tab (n_live x 2): the view and the hypotheses per block chosen for it.
-// modelsP (V x H x 12) the hypothesis projections, modelsCR (V x H x 12) their
+// Live views: n_v >= 6.  modelsP (V x H x 12) the hypothesis projections, modelsCR (V x H x 12) their
 // C | R; counts (V x H), 0 for a model that is not finite.
 __global__ void __launch_bounds__(RV_THREADS)
 k_reg_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_start,
@@ -152,18 +152,11 @@ k_reg_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_
     __shared__ double2 sxy[RV_TILE];
     __shared__ int32_t sFin[RV_HT], sCnt[RV_HT];
     const int tid = threadIdx.x;
-    // the live view of this block: the last j with blk_start[j] <= blockIdx.x
-    int lo = 0, hi = n_live - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (blk_start[mid] <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int32_t v = tab[2 * lo], ht = tab[2 * lo + 1];
-    const int32_t hb = ((int32_t)blockIdx.x - blk_start[lo]) * ht;
-    const int nh = min(ht, H - hb);
-    const int64_t vs = view_start[v];
-    const int n = (int)(view_start[v + 1] - vs);
-    const int64_t row0 = (int64_t)v * H + hb;
+    const HypTile t = tile_of_block(blk_start, tab, n_live, H);
+    const int nh = t.nh;
+    const int64_t vs = view_start[t.row];
+    const int n = (int)(view_start[t.row + 1] - vs);
+    const int64_t row0 = (int64_t)t.row * H + t.hb;
 
     // ---- fit: 16 hypotheses a pass, 16 lanes each
     const int k = tid & (RV_GROUP - 1);
@@ -218,36 +211,21 @@ k_reg_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const double thr2 = thr * thr;
-    for (int base = 0; base < n; base += RV_TILE) {
-        const int nt = min(RV_TILE, n - base);
-        for (int i = tid; i < nt; i += RV_THREADS) {
-            const int64_t c = vs + base + i;
-            const int64_t pi = pt_idx[c];
-            sX[3 * i] = Xg[3 * pi];
-            sX[3 * i + 1] = Xg[3 * pi + 1];
-            sX[3 * i + 2] = Xg[3 * pi + 2];
-            sxy[i] = xy[c];
-        }
-        __syncthreads();
-        for (int hl = wave; hl < nh; hl += RV_WAVES) {
-            if (!sFin[hl]) continue;
-            double P[12];
+    for_each_tile<RV_THREADS, RV_TILE>(
+        n, [&](int i, int c) { rv_stage(Xg, pt_idx, xy, vs + c, sX, sxy, i); },
+        [&](int nt) {
+            for (int hl = wave; hl < nh; hl += RV_WAVES) {
+                if (!sFin[hl]) continue;
+                double P[12];
 #pragma unroll
-            for (int j = 0; j < 12; ++j) P[j] = sP[hl][j];
-            int cnt = 0;
-            for (int j = 0; j < nt; j += 64) {
-                const int i = j + lane;
-                bool in = false;
-                if (i < nt) {
+                for (int j = 0; j < 12; ++j) P[j] = sP[hl][j];
+                const int cnt = wave_count(nt, [&](int i) {
                     const double2 q = sxy[i];
-                    in = rv_inlier(P, sX[3 * i], sX[3 * i + 1], sX[3 * i + 2], q.x, q.y, thr, thr2);
-                }
-                cnt += __popcll(__ballot(in));
+                    return rv_inlier(P, sX[3 * i], sX[3 * i + 1], sX[3 * i + 2], q.x, q.y, thr, thr2);
+                });
+                if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
             }
-            if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
-        }
-        __syncthreads();
-    }
+        });
     if (tid < nh) counts[row0 + tid] = sFin[tid] ? sCnt[tid] : 0;
 }
 
@@ -341,23 +319,11 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
     SFM_CHECK_ARG(view_start && K, "null pointer");
     SFM_TRY(check_csr(view_start, V, n_corr, "view_start", "correspondence", 0x7fffffff,
                       "a view has too many correspondences"));
-    int64_t n_live = 0;
-    for (int64_t v = 0; v < V; ++v) n_live += view_start[v + 1] - view_start[v] >= 6;
+    const int64_t n_live = count_live(view_start, V, 6);
     SFM_CHECK_ARG(n_corr == 0 || (pt_idx && xy && X), "null pointer");
     SFM_TRY(check_index(pt_idx, n_corr, n_pts, "point index outside [0, n_pts)"));
     SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    for (int64_t v = 0; v < V; ++v) {
-        const int64_t n = view_start[v + 1] - view_start[v];
-        if (n < 6) continue;
-        const int32_t *sv = samples + v * H * 6;
-        for (int64_t h = 0; h < H; ++h) {
-            const int32_t *s = sv + h * 6;
-            for (int a = 0; a < 6; ++a) {
-                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_v)");
-                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
-            }
-        }
-    }
+    SFM_TRY(check_samples(view_start, V, samples, H, 6, 6, "sample outside [0, n_v)"));
     if (V == 0) return 0;
     SFM_CHECK_ARG(C && R && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
                   "null pointer");
@@ -379,24 +345,8 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
 
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    int rc;
-    // block table: a view of many correspondences gets fewer hypotheses per
-    // block, so that its score loop is spread over more of them
-    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
-    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
-    int64_t blocks = 0, j = 0;
-    for (int64_t v = 0; v < V; ++v) {
-        const int64_t n = view_start[v + 1] - view_start[v];
-        if (n < 6) continue;
-        const int32_t ht = n >= 4 * RV_TILE ? RV_FIT : (n >= RV_TILE ? 2 * RV_FIT : RV_HT);
-        blk[j] = (int32_t)blocks;
-        tab[2 * j] = (int32_t)v;
-        tab[2 * j + 1] = ht;
-        blocks += (H + ht - 1) / ht;
-        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
-        ++j;
-    }
-    blk[n_live] = (int32_t)blocks;
+    TileTable tt;
+    SFM_TRY(tt.build(c->pinned, n_live, view_start, V, 6, H, RV_HT, RV_TILE));
 
     const size_t VH = (size_t)V * (size_t)H;
     Pack in(c->buf[0]), out(c->buf[1]);
@@ -404,7 +354,7 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
     const auto i_xy = in.add<double2>(n_corr);
     const auto i_X = in.add<double>(3 * n_pts);
     const auto i_pt = in.add<int32_t>(n_corr), i_s = in.add<int32_t>(6 * VH);
-    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto i_t = in.add<int32_t>(tt.words());  // the block table
     const auto o_C = out.add<double>(3 * V), o_R = out.add<double>(9 * V), o_cost = out.add<double>(V);
     const auto o_info = out.add<int32_t>(V), o_ninl = out.add<int32_t>(V);
     const auto o_hyp = out.add<int32_t>(V), o_bc = out.add<int32_t>(V), o_cnt = out.add<int32_t>(VH);
@@ -422,9 +372,9 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
     SFM_TRY(in.upload(i_X, X, s));
     SFM_TRY(in.upload(i_pt, pt_idx, s));
     SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(in.upload(i_t, tt.blk, s));
     SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_reg_fit_score, dim3((unsigned)blocks), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
+    hipLaunchKernelGGL(k_reg_fit_score, dim3((unsigned)tt.blocks), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
                        in.ptr(i_pt), in.ptr(i_xy), in.ptr(i_s), (int32_t)H, cam, in.ptr(i_t),
                        in.ptr(i_t, n_live + 1), (int32_t)n_live, threshold, out.ptr(o_mP), out.ptr(o_mCR),
                        out.ptr(o_cnt));
@@ -437,28 +387,17 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
                        out.ptr(o_mask));
     SFM_HIP(hipGetLastError());
     SFM_TRY(tm.mark(s));
-    // live views are copied out one run of consecutive views at a time, so that
-    // what the host wrote for the views of info -1 stays
-    for (int64_t v0 = 0; v0 < V;) {
-        if (view_start[v0 + 1] - view_start[v0] < 6) {
-            ++v0;
-            continue;
-        }
-        int64_t v1 = v0;
-        while (v1 < V && view_start[v1 + 1] - view_start[v1] >= 6) ++v1;
-        const size_t nv = (size_t)(v1 - v0);
-        SFM_TRY(out.download(C + 3 * v0, o_C, 3 * v0, 3 * nv, s));
-        SFM_TRY(out.download(R + 9 * v0, o_R, 9 * v0, 9 * nv, s));
-        SFM_TRY(out.download(cost + v0, o_cost, v0, nv, s));
-        SFM_TRY(out.download(info + v0, o_info, v0, nv, s));
-        SFM_TRY(out.download(n_inliers + v0, o_ninl, v0, nv, s));
-        SFM_TRY(out.download(best_hyp + v0, o_hyp, v0, nv, s));
-        SFM_TRY(out.download(best_count + v0, o_bc, v0, nv, s));
-        const int64_t k0 = view_start[v0], k1 = view_start[v1];
-        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
-        if (counts) SFM_TRY(out.download(counts + v0 * H, o_cnt, v0 * H, nv * H, s));
-        if (models) SFM_TRY(out.download(models + v0 * H * 12, o_mP, v0 * H * 12, nv * H * 12, s));
-        v0 = v1;
-    }
+    SFM_TRY(for_each_live_run(view_start, V, 6, [&](int64_t v0, int64_t v1, int64_t k0, int64_t k1) -> int {
+        SFM_TRY(out.download_rows(C, o_C, 3, v0, v1, s));
+        SFM_TRY(out.download_rows(R, o_R, 9, v0, v1, s));
+        SFM_TRY(out.download_rows(cost, o_cost, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(info, o_info, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(best_count, o_bc, 1, v0, v1, s));
+        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
+        SFM_TRY(out.download_rows(counts, o_cnt, H, v0, v1, s));
+        return out.download_rows(models, o_mP, 12 * H, v0, v1, s);
+    }));
     return tm.finish(s);
 }

@@ -51,6 +51,10 @@ class Pack {
         if (count && host) SFM_HIP(hipMemcpyAsync(host, ptr(s, first), count * sizeof(T), hipMemcpyDeviceToHost, st));
         return 0;
     }
+    // rows [r0, r1) of `per` elements each, to their place in the host array of all rows
+    template <class T> int download_rows(T *host, Slot<T> s, size_t per, int64_t r0, int64_t r1, hipStream_t st) const {
+        return host ? download(host + per * r0, s, per * r0, per * (size_t)(r1 - r0), st) : 0;
+    }
 
   private:
     static void require(bool ok, const char *what) {

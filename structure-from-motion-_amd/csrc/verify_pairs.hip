@@ -9,11 +9,12 @@
 // bit.  This entry point uses x2^T F x1 = 0 throughout, a unit-norm model and
 // the Sampson distance (epi_sampson.hpp).  Differs on purpose.
 //
-//   k_vp_fit_score  flat grid over (pair, hypothesis tile) from a host prefix
-//                   table.  Fit: a hypothesis belongs to 8 lanes, one design row
-//                   each (vp_fit_group8).  Score: the pair's correspondences are
-//                   staged through LDS in tiles of 1024, a wave per hypothesis,
-//                   ballot popcount of the inlier rule.
+// The grid, the block table, the tile loop and the fixed-order sums are the
+// scaffold's (hyp_batch.hpp).
+//
+//   k_vp_fit_score  Fit: a hypothesis belongs to 8 lanes, one design row each
+//                   (vp_fit_group8).  Score: a wave per hypothesis, the inlier
+//                   rule over tiles of 1024.
 //   k_vp_refit      one workgroup per pair: winner (most inliers, then the
 //                   earliest), its mask, then rounds of the normalised
 //                   least-squares fit over the current inliers (Hartley sums,
@@ -21,17 +22,15 @@
 //                   the 9 x 9 factors in LDS, one lane's 9-column Jacobi), a
 //                   re-score of the whole pair and the not-worse test.
 //
-// Every sum runs in a fixed order over quantities of the pair alone (strided
-// per-thread partial sums, a 64-lane butterfly, the two wave results added);
-// the factors merge along a fixed tree; counts are integers.  A pair's outputs
-// therefore do not depend on the batch it is in.
+// The factors merge along a fixed tree, so a pair's outputs do not depend on
+// the batch it is in.
 #include <cmath>
 #include <cstring>
 
 #include "dlt_general.hpp"
 #include "epi_sampson.hpp"
+#include "hyp_batch.hpp"
 #include "select.hpp"
-#include "staging.hpp"
 
 #pragma clang fp contract(off)
 
@@ -44,11 +43,9 @@ constexpr int VP_HT = 64;                      // most hypotheses per workgroup
 constexpr int VP_TILE = 1024;                  // correspondences per LDS tile (32 KiB)
 constexpr int VP_RT = FG_THREADS;              // refit: 128 threads of 45 doubles, 45 KiB of LDS
 constexpr int VP_RW = VP_RT / 64;
-static_assert(VP_RW == 2, "vp_wg_sum adds two wave results");
 
-// blk_start (n_live + 1): the first block of each live pair (n_p >= 8); tab
-// (n_live x 2): the pair and the hypotheses per block chosen for it.  models
-// (P x H x 9); counts (P x H), 0 for a model that is not finite.
+// Live pairs: n_p >= 8.  models (P x H x 9); counts (P x H), 0 for a model that
+// is not finite.
 __global__ void __launch_bounds__(VP_THREADS)
 k_vp_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x1,
                const double2 *__restrict__ x2, const int32_t *__restrict__ samples, int32_t H,
@@ -59,18 +56,11 @@ k_vp_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict
     __shared__ double2 s2[VP_TILE];
     __shared__ int32_t sFin[VP_HT], sCnt[VP_HT];
     const int tid = threadIdx.x;
-    // the live pair of this block: the last j with blk_start[j] <= blockIdx.x
-    int lo = 0, hi = n_live - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (blk_start[mid] <= (int32_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int32_t p = tab[2 * lo], ht = tab[2 * lo + 1];
-    const int32_t hb = ((int32_t)blockIdx.x - blk_start[lo]) * ht;
-    const int nh = min(ht, H - hb);
-    const int64_t ps = pair_start[p];
-    const int n = (int)(pair_start[p + 1] - ps);
-    const int64_t row0 = (int64_t)p * H + hb;
+    const HypTile t = tile_of_block(blk_start, tab, n_live, H);
+    const int nh = t.nh;
+    const int64_t ps = pair_start[t.row];
+    const int n = (int)(pair_start[t.row + 1] - ps);
+    const int64_t row0 = (int64_t)t.row * H + t.hb;
 
     // ---- fit: 32 hypotheses a pass, 8 lanes each
     const int k = tid & 7;
@@ -108,80 +98,26 @@ k_vp_fit_score(const int64_t *__restrict__ pair_start, const double2 *__restrict
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const double thr2 = thr * thr;
-    for (int base = 0; base < n; base += VP_TILE) {
-        const int nt = min(VP_TILE, n - base);
-        for (int i = tid; i < nt; i += VP_THREADS) {
-            s1[i] = x1[ps + base + i];
-            s2[i] = x2[ps + base + i];
-        }
-        __syncthreads();
-        for (int hl = wave; hl < nh; hl += VP_WAVES) {
-            if (!sFin[hl]) continue;
-            double F[9];
+    for_each_tile<VP_THREADS, VP_TILE>(
+        n, [&](int i, int c) { s1[i] = x1[ps + c], s2[i] = x2[ps + c]; },
+        [&](int nt) {
+            for (int hl = wave; hl < nh; hl += VP_WAVES) {
+                if (!sFin[hl]) continue;
+                double F[9];
 #pragma unroll
-            for (int j = 0; j < 9; ++j) F[j] = sF[hl][j];
-            int cnt = 0;
-            for (int j = 0; j < nt; j += 64) {
-                const int i = j + lane;
-                bool in = false;
-                if (i < nt) {
+                for (int j = 0; j < 9; ++j) F[j] = sF[hl][j];
+                const int cnt = wave_count(nt, [&](int i) {
                     const double2 q1 = s1[i], q2 = s2[i];
                     double e2, den;
-                    in = vp_inlier(F, q1.x, q1.y, q2.x, q2.y, thr2, e2, den);
-                }
-                cnt += __popcll(__ballot(in));
+                    return vp_inlier(F, q1.x, q1.y, q2.x, q2.y, thr2, e2, den);
+                });
+                if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
             }
-            if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
-        }
-        __syncthreads();
-    }
+        });
     if (tid < nh) counts[row0 + tid] = sFin[tid] ? sCnt[tid] : 0;
 }
 
 // ------------------------------------------------------------------ phase 2
-// Fixed-order sum of NV values over the workgroup: a 64-lane butterfly (both
-// partners add the same pair, so every lane holds the same bits), then the two
-// wave results.  red: VP_RW x NV.
-template <int NV>
-__device__ __forceinline__ void vp_wg_sum(double (&x)[NV], double (*red)[NV]) {
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) x[j] += __shfl_xor(x[j], w);
-    __syncthreads();  // the last use of red is over
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) red[threadIdx.x >> 6][j] = x[j];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NV; ++j) x[j] = red[0][j] + red[1][j];
-}
-
-struct VpPair {
-    const double2 *x1, *x2;  // the pair's first correspondence
-    int n;
-};
-
-// mask[i] = the inlier rule under F for the pair's correspondence i; count and
-// the inliers' squared Sampson distances summed (thread t owns i = t, t + 128, ...)
-__device__ __forceinline__ void vp_mask(const VpPair &w, const double *F, double thr2, uint8_t *mask, int &count,
-                                        double &cost, double (*red)[4]) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < w.n; i += VP_RT) {
-        const double2 p = w.x1[i], q = w.x2[i];
-        double e2, den;
-        const bool in = vp_inlier(F, p.x, p.y, q.x, q.y, thr2, e2, den);
-        mask[i] = in ? 1 : 0;
-        if (in) {
-            acc[0] += 1.0;
-            acc[1] += e2 / den;
-        }
-    }
-    vp_wg_sum<4>(acc, red);
-    count = (int)acc[0];
-    cost = acc[1];
-}
-
 // jacobi_onesided<9, 9, 40> and weakest_column on a matrix in LDS, for one
 // lane: a[9 j + i] is column j, row i; V (9 x 9, row-major) accumulates the
 // rotations.  The same rotation rule, threshold and sweep cap; held in
@@ -247,7 +183,7 @@ __device__ __forceinline__ int vp_jacobi9(double *a, double *V) {
 // and the LDS tree merge of k_dlt_general, then thread 0's one-sided Jacobi
 // for the right singular vector of the least singular value and vp_finish.
 // F to every thread, through sFn.
-__device__ __forceinline__ void vp_refit(const VpPair &w, const uint8_t *mask, int n_in, double (*red)[4],
+__device__ __forceinline__ void vp_refit(const EpiPair &w, const uint8_t *mask, int n_in, double (*red)[4],
                                          double (*Rs)[45], double *sFn, double (&F)[9]) {
     const int t = threadIdx.x;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -256,7 +192,7 @@ __device__ __forceinline__ void vp_refit(const VpPair &w, const uint8_t *mask, i
         const double2 p = w.x1[i], q = w.x2[i];
         s[0] += p.x; s[1] += p.y; s[2] += q.x; s[3] += q.y;
     }
-    vp_wg_sum<4>(s, red);
+    wg_sum<VP_RW, 4>(s, red);
     const double N = (double)n_in;
     const double m1x = s[0] / N, m1y = s[1] / N, m2x = s[2] / N, m2y = s[3] / N;
     double d[4] = {0.0, 0.0, 0.0, 0.0};
@@ -267,7 +203,7 @@ __device__ __forceinline__ void vp_refit(const VpPair &w, const uint8_t *mask, i
         d[0] += sqrt(ax * ax + ay * ay);
         d[1] += sqrt(bx * bx + by * by);
     }
-    vp_wg_sum<4>(d, red);
+    wg_sum<VP_RW, 4>(d, red);
     Hartley h1, h2;
     h1.s = 1.4142135623730951 / (d[0] / N + 1e-8);
     h2.s = 1.4142135623730951 / (d[1] / N + 1e-8);
@@ -345,7 +281,7 @@ k_vp_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
     const int64_t ps = pair_start[p];
     const int n = (int)(pair_start[p + 1] - ps);
     if (n < 8) return;
-    const VpPair w{x1 + ps, x2 + ps, n};
+    const EpiPair w{x1 + ps, x2 + ps, n};
     uint8_t *mask = inlier + ps, *trial = mask2 + ps;
     const double thr2 = thr * thr;
 
@@ -375,25 +311,18 @@ k_vp_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
         const double *m = models + (p * H + bh) * 9;
 #pragma unroll
         for (int j = 0; j < 9; ++j) F[j] = m[j];
-        vp_mask(w, F, thr2, mask, n_inl, cost, red);
+        epi_mask<VP_RT>(w, F, thr2, mask, n_inl, cost, red);
         info = -3;
         if (bc >= min_inliers) {
             info = refit_rounds > 0 ? 2 : 0;
             for (int round = 0; round < refit_rounds; ++round) {
                 if (n_inl < 8) break;
-                // (a thread reads and writes the masks at its own i = t, t + 128, ... alone)
                 double Fn[9], cost2;
                 int n2;
                 vp_refit(w, mask, n_inl, red, Rs, sFn, Fn);
-                vp_mask(w, Fn, thr2, trial, n2, cost2, red);
-                // the refitted state replaces the current one only if it is not worse
-                if (!(n2 > n_inl || (n2 == n_inl && cost2 <= cost))) break;
-                int changed = 0;
-                for (int i = tid; i < n; i += VP_RT) {
-                    changed |= mask[i] != trial[i];
-                    mask[i] = trial[i];
-                }
-                changed = __syncthreads_or(changed);
+                epi_mask<VP_RT>(w, Fn, thr2, trial, n2, cost2, red);
+                if (!not_worse(n2, cost2, n_inl, cost)) break;
+                const int changed = adopt_trial<VP_RT>(mask, trial, n);
 #pragma unroll
                 for (int j = 0; j < 9; ++j) F[j] = Fn[j];
                 n_inl = n2;
@@ -433,22 +362,10 @@ extern "C" int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const doub
     SFM_CHECK_ARG(pair_start, "null pointer");
     SFM_TRY(check_csr(pair_start, P, n_corr, "pair_start", "correspondence", 0x7fffffff,
                       "a pair has too many correspondences"));
-    int64_t n_live = 0;
-    for (int64_t p = 0; p < P; ++p) n_live += pair_start[p + 1] - pair_start[p] >= 8;
+    const int64_t n_live = count_live(pair_start, P, 8);
     SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
     SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t n = pair_start[p + 1] - pair_start[p];
-        if (n < 8) continue;
-        const int32_t *sp = samples + p * H * 8;
-        for (int64_t h = 0; h < H; ++h) {
-            const int32_t *s = sp + h * 8;
-            for (int a = 0; a < 8; ++a) {
-                SFM_CHECK_ARG(s[a] >= 0 && s[a] < n, "sample outside [0, n_p)");
-                for (int b = 0; b < a; ++b) SFM_CHECK_ARG(s[a] != s[b], "a hypothesis repeats a sample");
-            }
-        }
-    }
+    SFM_TRY(check_samples(pair_start, P, samples, H, 8, 8, "sample outside [0, n_p)"));
     if (P == 0) return 0;
     SFM_CHECK_ARG(F && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
                   "null pointer");
@@ -469,31 +386,15 @@ extern "C" int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const doub
 
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
-    int rc;
-    // block table: a pair of many correspondences gets fewer hypotheses per
-    // block, so that its score loop is spread over more of them
-    if ((rc = c->pinned.reserve((size_t)(3 * n_live + 1) * sizeof(int32_t)))) return rc;
-    int32_t *blk = c->pinned.as<int32_t>(), *tab = blk + (n_live + 1);
-    int64_t blocks = 0, j = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const int64_t n = pair_start[p + 1] - pair_start[p];
-        if (n < 8) continue;
-        const int32_t ht = n >= 4 * VP_TILE ? VP_HT / 4 : (n >= VP_TILE ? VP_HT / 2 : VP_HT);
-        blk[j] = (int32_t)blocks;
-        tab[2 * j] = (int32_t)p;
-        tab[2 * j + 1] = ht;
-        blocks += (H + ht - 1) / ht;
-        SFM_CHECK_ARG(blocks <= (int64_t)0x7fffffff, "too many hypothesis tiles for one launch");
-        ++j;
-    }
-    blk[n_live] = (int32_t)blocks;
+    TileTable tt;
+    SFM_TRY(tt.build(c->pinned, n_live, pair_start, P, 8, H, VP_HT, VP_TILE));
 
     const size_t PH = (size_t)P * (size_t)H;
     Pack in(c->buf[0]), out(c->buf[1]);
     const auto i_ps = in.add<int64_t>(P + 1);
     const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
     const auto i_s = in.add<int32_t>(8 * PH);
-    const auto i_t = in.add<int32_t>(3 * n_live + 1);  // the block table
+    const auto i_t = in.add<int32_t>(tt.words());  // the block table
     const auto o_F = out.add<double>(9 * P), o_cost = out.add<double>(P);
     const auto o_info = out.add<int32_t>(P), o_ninl = out.add<int32_t>(P);
     const auto o_hyp = out.add<int32_t>(P), o_bc = out.add<int32_t>(P), o_cnt = out.add<int32_t>(PH);
@@ -508,9 +409,9 @@ extern "C" int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const doub
     SFM_TRY(in.upload(i_x1, x1, s));
     SFM_TRY(in.upload(i_x2, x2, s));
     SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, blk, s));
+    SFM_TRY(in.upload(i_t, tt.blk, s));
     SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_vp_fit_score, dim3((unsigned)blocks), dim3(VP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
+    hipLaunchKernelGGL(k_vp_fit_score, dim3((unsigned)tt.blocks), dim3(VP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
                        in.ptr(i_x2), in.ptr(i_s), (int32_t)H, in.ptr(i_t), in.ptr(i_t, n_live + 1), (int32_t)n_live,
                        threshold, out.ptr(o_m), out.ptr(o_cnt));
     SFM_HIP(hipGetLastError());
@@ -521,27 +422,16 @@ extern "C" int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const doub
                        out.ptr(o_info), out.ptr(o_mask));
     SFM_HIP(hipGetLastError());
     SFM_TRY(tm.mark(s));
-    // live pairs are copied out one run of consecutive pairs at a time, so that
-    // what the host wrote for the pairs of info -1 stays
-    for (int64_t p0 = 0; p0 < P;) {
-        if (pair_start[p0 + 1] - pair_start[p0] < 8) {
-            ++p0;
-            continue;
-        }
-        int64_t p1 = p0;
-        while (p1 < P && pair_start[p1 + 1] - pair_start[p1] >= 8) ++p1;
-        const size_t np = (size_t)(p1 - p0);
-        SFM_TRY(out.download(F + 9 * p0, o_F, 9 * p0, 9 * np, s));
-        SFM_TRY(out.download(cost + p0, o_cost, p0, np, s));
-        SFM_TRY(out.download(info + p0, o_info, p0, np, s));
-        SFM_TRY(out.download(n_inliers + p0, o_ninl, p0, np, s));
-        SFM_TRY(out.download(best_hyp + p0, o_hyp, p0, np, s));
-        SFM_TRY(out.download(best_count + p0, o_bc, p0, np, s));
-        const int64_t k0 = pair_start[p0], k1 = pair_start[p1];
-        SFM_TRY(out.download(inlier + k0, o_mask, k0, k1 - k0, s));
-        if (counts) SFM_TRY(out.download(counts + p0 * H, o_cnt, p0 * H, np * H, s));
-        if (models) SFM_TRY(out.download(models + p0 * H * 9, o_m, p0 * H * 9, np * H * 9, s));
-        p0 = p1;
-    }
+    SFM_TRY(for_each_live_run(pair_start, P, 8, [&](int64_t p0, int64_t p1, int64_t k0, int64_t k1) -> int {
+        SFM_TRY(out.download_rows(F, o_F, 9, p0, p1, s));
+        SFM_TRY(out.download_rows(cost, o_cost, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(info, o_info, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(best_count, o_bc, 1, p0, p1, s));
+        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
+        SFM_TRY(out.download_rows(counts, o_cnt, H, p0, p1, s));
+        return out.download_rows(models, o_m, 9 * H, p0, p1, s);
+    }));
     return tm.finish(s);
 }
