@@ -843,6 +843,11 @@ int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *opts, sfm_ba_report *repo
  * environment has SFM_PLAN_DIGEST=1, else 0): the device planner and the
  * host planner (SFM_PLAN_HOST=1) must produce the same plan */
 int sfm_ba_plan_digest(sfm_ba_problem *p, uint64_t *out);
+/* the speculative sweep's dispatch (the rejection branch's Schur system built
+ * beside the reduced solve): out = {free CUs, whole (spec, range) items,
+ * split specs, sub-ranges per split item (0: no split)}; all 0 when the
+ * problem cannot speculate (several ranks, the Cholesky fallback) */
+int sfm_ba_spec_plan(sfm_ba_problem *p, int32_t out[4]);
 /* reset the device state to the initial parameters given at create time */
 int sfm_ba_reset(sfm_ba_problem *p);
 int sfm_ba_download(sfm_ba_problem *p, double *cam_params, double *points);

@@ -135,6 +135,7 @@ SIGNATURES = [
     ("sfm_ba_solve", _c, [ctypes.c_void_p, ctypes.POINTER(BAOpts), ctypes.POINTER(BAReport)]),
     ("sfm_ba_reset", _c, [ctypes.c_void_p]),
     ("sfm_ba_plan_digest", _c, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("sfm_ba_spec_plan", _c, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     ("sfm_ba_download", _c, [ctypes.c_void_p, _d, _d]),
     ("sfm_ba_kernel_times", _c, [ctypes.c_void_p, _d, _c, ctypes.c_char_p, _c]),
     ("sfm_ba_set_timing", _c, [ctypes.c_void_p, _c]),
@@ -1448,6 +1449,13 @@ class BAProblem:
         d = ctypes.c_uint64()
         _check(_lib.sfm_ba_plan_digest(self.h, ctypes.byref(d)))
         return d.value
+
+    def spec_plan(self):
+        """The speculative sweep's dispatch (sfm_ba_spec_plan): free CUs, whole
+        items, split specs, sub-ranges per split item."""
+        out = (ctypes.c_int32 * 4)()
+        _check(_lib.sfm_ba_spec_plan(self.h, out))
+        return dict(zip(("free_cus", "whole_items", "split_specs", "sub_ranges"), out))
 
     def download(self):
         cams = np.zeros((self.n_cams, 6))

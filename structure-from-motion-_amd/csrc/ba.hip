@@ -1076,15 +1076,15 @@ __global__ void __launch_bounds__(SW_THREADS) k_schur_sweep(
             const int x = blockIdx.x % NXCD;
             w = (int)(blockIdx.x / NXCD) * (NXCD / nrange) + x / nrange;
             r = x % nrange;
-            if (w >= nspec) return;  // whole workgroup
+            if (w >= (sp.S > 0 ? sp.w0 : nspec)) return;  // whole workgroup
         }
         if (r >= nrange) return;  // whole workgroup
         q0 = rchunk[r];
         q1 = rchunk[r + 1];
         slab_out = slab + (int64_t)r * nbd * ITEM_W;
     } else {
-        const int u = blockIdx.x - sp.nfull, v = u / NXCD, s = v % sp.S;
-        r = u % NXCD;
+        const int u = blockIdx.x - sp.nfull, v = u / nrange, s = v % sp.S;  // (a split plan has at most NXCD ranges)
+        r = u % nrange;
         w = sp.w0 + v / sp.S;
         const int Q0 = rchunk[r], Q1 = rchunk[r + 1];
         q0 = Q0 + (Q1 - Q0) * s / sp.S;
@@ -1960,6 +1960,17 @@ struct LMState {
     double lambda, nu, cost, cost0;
     int status, accepted, iters, done;
     int run_lin, run_step, accept_now, pad;
+    // Speculation (sfm_ba_solve): beside this iteration's reduced solve the
+    // damped Schur system of its rejection branch is built at spec_lambda =
+    // lambda * nu (run_spec gates that chain).  When the step is then
+    // rejected, the next iteration's damping is exactly that value: use_spec
+    // is set, its own prep / sweep / finish are gated off (run_real) and its
+    // solve and trial read the speculated buffers.
+    double spec_lambda;
+    int armed;     // a step of this solve was rejected: stays set
+    int use_spec;  // this iteration's system is the one speculated beside the last solve
+    int run_real;  // run_step && !use_spec: gates this iteration's own prep / sweep / finish
+    int run_spec;  // run_step && armed: gates the speculative chain
 };
 
 // The host's view of the LM state: k_lm_step of iteration it publishes its
@@ -1989,7 +2000,8 @@ __global__ void __launch_bounds__(256) k_gather_cam_major(int64_t no, const int3
 __global__ void k_lm_reset(LMState *lm, double lambda0, int *bad) {
     lm->lambda = lambda0; lm->nu = 2.0; lm->cost = 0.0; lm->cost0 = 0.0;
     lm->status = 4; lm->accepted = 0; lm->iters = 0; lm->done = 0;
-    lm->run_lin = 1; lm->run_step = 1; lm->accept_now = 0;
+    lm->run_lin = 1; lm->run_step = 1; lm->accept_now = 0; lm->pad = 0;
+    lm->spec_lambda = lambda0 * 2.0; lm->armed = 0; lm->use_spec = 0; lm->run_real = 1; lm->run_spec = 0;
     bad[0] = 0;
 }
 
@@ -2004,17 +2016,24 @@ __global__ void k_lm_init(LMState *lm, const double *lin_cost) {
         lm->done = 1;
         lm->run_step = 0;
         lm->run_lin = 0;
+        lm->run_real = 0;
+        lm->run_spec = 0;
     }
 }
 
 // sfm_ba_solve's host logic, verbatim: Nielsen's lambda update on the gain
 // ratio of the trial step; scal = [cost_trial, model_p, dn_p, xn_p, model_c,
 // dn_c, xn_c].  Returns the new state from the old one (a pure function, so
-// every block of k_lm_step computes the same decision).
+// every block of k_lm_step computes the same decision).  spec: bit 0, this
+// solve speculates (a rejection arms it); bit 1, the host queued the
+// speculative chain beside this iteration's solve.
 __device__ __forceinline__ LMState lm_decide(LMState lm, const double *__restrict__ h, int bad, int max_iterations,
-                                             int fixed, double ftol, double ptol, double lambda0) {
+                                             int fixed, double ftol, double ptol, double lambda0, int spec) {
 #pragma clang fp contract(off)
     if (lm.done) { lm.accept_now = 0; return lm; }
+    // the speculated system exists if its chain was queued and ran, at this damping
+    const bool built = (spec & 2) && lm.run_spec;
+    const double built_lambda = lm.spec_lambda;
     const double cost = lm.cost;
     const double cost_new = h[0];
     const double model = 0.5 * (h[1] + h[4]);
@@ -2050,6 +2069,14 @@ __device__ __forceinline__ LMState lm_decide(LMState lm, const double *__restric
     lm.done = done;
     lm.run_step = !done;
     lm.run_lin = lm.run_lin && !done;
+    // after a rejection the linearisation stands and lambda is the product the
+    // speculative prep formed (the same multiply, so the same bits; the
+    // lambda0 restart past 1e32 is not)
+    lm.armed = lm.armed || ((spec & 1) && !lm.accept_now);
+    lm.use_spec = built && !lm.accept_now && !done && lm.lambda == built_lambda;
+    lm.spec_lambda = lm.lambda * lm.nu;
+    lm.run_real = lm.run_step && !lm.use_spec;
+    lm.run_spec = lm.run_step && lm.armed;
     return lm;
 }
 
@@ -2083,6 +2110,8 @@ __global__ void k_gtol_check(int32_t nc, double gtol, const double *__restrict__
         lm->done = 1;
         lm->run_step = 0;
         lm->run_lin = 0;
+        lm->run_real = 0;
+        lm->run_spec = 0;
     }
 }
 
@@ -2095,8 +2124,8 @@ __global__ void k_lm_step(const LMState *__restrict__ lm_in, LMState *__restrict
                           const double *__restrict__ h, const int *__restrict__ bad_in, int *__restrict__ bad_next,
                           int max_iterations, int fixed, double ftol, double ptol, double lambda0, int64_t np_,
                           int32_t nc, double *__restrict__ X, const double *__restrict__ X2, double *__restrict__ Rt,
-                          const double *__restrict__ Rt2, HostLM *__restrict__ ring, int seq) {
-    const LMState lm = lm_decide(*lm_in, h, *bad_in, max_iterations, fixed, ftol, ptol, lambda0);
+                          const double *__restrict__ Rt2, HostLM *__restrict__ ring, int seq, int spec) {
+    const LMState lm = lm_decide(*lm_in, h, *bad_in, max_iterations, fixed, ftol, ptol, lambda0, spec);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *lm_out = lm;
         *bad_next = 0;
@@ -2269,9 +2298,12 @@ extern "C" int sfm_gj_debug(long long *out, int64_t n) {
 }
 
 static int launch_gj(const GjPlan &g, int nT, int32_t ns, const double *payload, const double *lam, const GjBufs &b, int epoch, double *x, int *bad, const int *gate,
-                     const CamTrialArgs &ct, hipStream_t s) {
+                     const CamTrialArgs &ct, hipStream_t s, const double *payload_spec = nullptr,
+                     const int *use_spec = nullptr) {
     gj::Args a;
     a.payload = payload;
+    a.payload_spec = payload_spec;
+    a.use_spec = use_spec;
     a.ns = ns;
     a.nT = nT;
     a.cb = g.cb;
@@ -2356,10 +2388,13 @@ struct GjrBufs {
 };
 static int launch_gjr(const GjrPlan &g, int32_t ns, const double *payload, const double *lam, const GjrBufs &b,
                       unsigned tag, double *x, int *bad, const int *gate, const CamTrialArgs &ct, hipStream_t s,
-                      const SlabSrc &src = SlabSrc{nullptr, nullptr, 0, 0, {}, nullptr}) {
+                      const SlabSrc &src = SlabSrc{nullptr, nullptr, 0, 0, {}, nullptr},
+                      const double *payload_spec = nullptr, const int *use_spec = nullptr) {
     gjr::Args a;
     a.src = src;
     a.payload = payload;
+    a.payload_spec = payload_spec;
+    a.use_spec = use_spec;
     a.ns = ns;
     a.nT = g.nT;
     a.lam = lam;
@@ -2410,7 +2445,9 @@ __global__ void __launch_bounds__(NT) k_backsub_trial(int64_t np_, int32_t nc, c
                                                               const int32_t *__restrict__ cam,
                                                               const double2 *__restrict__ obs, Kmat Km,
                                                               const double *__restrict__ Vg,
-                                                              const double *__restrict__ Lq,
+                                                              const double *__restrict__ Lq_own,
+                                                              const double *__restrict__ Lq_spec,
+                                                              const int *__restrict__ use_spec,
                                                               const double *__restrict__ dc, const double *__restrict__ lam,
                                                               const double *__restrict__ Rt,
                                                               const double *__restrict__ Rt_new,
@@ -2420,6 +2457,8 @@ __global__ void __launch_bounds__(NT) k_backsub_trial(int64_t np_, int32_t nc, c
                                                               const int *__restrict__ gate) {
     if (gate && !*gate) return;  // device-side LM control: iteration gated off
     const double lambda = *lam;
+    // the factors of the system the solve used: this iteration's own, or the speculated one
+    const double *__restrict__ Lq = use_spec && *use_spec ? Lq_spec : Lq_own;
     double K[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) K[i] = Km.k[i];
@@ -3819,6 +3858,34 @@ enum { T_LIN, T_PREP, T_SCHUR, T_COMM, T_SOLVE, T_TRIAL, T_NT };
 constexpr int kEvSlots = 16;  // max iterations per batch between host polls
 static const char *kTimerNames = "linearize;point_prep;schur_blocks;allreduce;cholesky;backsub_trial";
 
+// The speculative chain's stream and events: `fork` marks "this iteration's
+// payload is finished" on the problem's stream, `join` the chain's end on the
+// second one (rings: an event is not re-recorded while a wait on it may be
+// pending); tm = {prep start, prep end, sweep start, finish end} per timing slot.
+constexpr int kSpecRing = 4;
+struct SpecKit {
+    hipStream_t stream = nullptr;
+    hipEvent_t fork[kSpecRing] = {}, join[kSpecRing] = {};
+    hipEvent_t tm[4 * kEvSlots] = {};
+    int make(bool timed) {  // (the timing events only for a timed solve: they are most of the cost)
+        if (!stream) {
+            SFM_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            for (auto &e : fork) SFM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (auto &e : join) SFM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        if (timed && !tm[0])
+            for (auto &e : tm) SFM_HIP(hipEventCreate(&e));
+        return 0;
+    }
+    void destroy() {
+        for (auto &e : fork) if (e) (void)hipEventDestroy(e);
+        for (auto &e : join) if (e) (void)hipEventDestroy(e);
+        for (auto &e : tm) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+        *this = SpecKit{};
+    }
+};
+
 struct sfm_ba_problem {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -3883,6 +3950,20 @@ struct sfm_ba_problem {
     unsigned gjr_tag = 0;
     bool gjr_fold = false;  // fold k_schur_finish into the row-distributed solve (SFM_GJR_FOLD)
     hipEvent_t ev_solve = nullptr;
+    // Speculation: the rejection branch's damped system built on a second
+    // stream beside the reduced solve (run_step / sfm_ba_solve).  The chain of
+    // iteration it writes set it & 1, the next iteration's solve and trial
+    // read it when the step was rejected.
+    bool spec_ok = false;       // create: one rank, persistent solve, the buffers below exist
+    bool spec_on = false;       // this solve speculates once a step was rejected
+    bool spec_armed = false;    // this solve: the host queues the speculative chain
+    SweepSplit sp_split = {};   // the speculative sweep's dispatch: the items past the free CUs cut into S
+    int32_t sp_free_cus = 0;    // CUs beside the persistent solve (SFM_SPEC_FREE_CUS)
+    int32_t *d_sp_split_of = nullptr;
+    double *d_sp_slab = nullptr;
+    double *d_sp_Lq[2] = {nullptr, nullptr}, *d_sp_payload[2] = {nullptr, nullptr};
+    SpecKit sk;                 // second stream and its events (made on first use, kept with the StreamKit)
+    bool sp_queued[kEvSlots] = {};  // timing: the iterations of the batch that carried a speculative chain
     double t_acc[T_NT] = {};
     int t_iters = 0;
     std::vector<std::pair<void *, size_t>> allocs;
@@ -3893,7 +3974,8 @@ struct sfm_ba_problem {
             if (comm->local->last_solve == ev_solve) comm->local->last_solve = nullptr;
         }
         // the stream drains before its blocks and events go back to the caches
-        const bool idle = stream && hipStreamSynchronize(stream) == hipSuccess;
+        const bool idle = stream && hipStreamSynchronize(stream) == hipSuccess &&
+                          (!sk.stream || hipStreamSynchronize(sk.stream) == hipSuccess);
         for (auto &a : allocs) {
             if (idle) pool_free(a.first, a.second, device);
             else (void)hipFree(a.first);
@@ -3909,6 +3991,7 @@ struct sfm_ba_problem {
         for (auto &e : ev_it)
             if (e) (void)hipEventDestroy(e);
         if (ev_solve) (void)hipEventDestroy(ev_solve);
+        sk.destroy();
         if (stream) (void)hipStreamDestroy(stream);
     }
     template <class T> int alloc(T *&p, int64_t n) {
@@ -3936,6 +4019,7 @@ struct StreamKit {
     hipEvent_t ev_it[2 * T_NT * kEvSlots];
     hipEvent_t ev_solve;
     HostLM *h_ring, *d_ring;
+    SpecKit sk;
 };
 static std::mutex &kit_mu() {
     static auto *m = new std::mutex();
@@ -3954,6 +4038,7 @@ void sfm_ba_problem::kit_release(sfm_ba_problem &p) {
     k.ev_solve = p.ev_solve;
     k.h_ring = p.h_ring;
     k.d_ring = p.d_ring;
+    k.sk = p.sk;
     std::lock_guard<std::mutex> lk(kit_mu());
     kits().push_back(k);
 }
@@ -3970,6 +4055,7 @@ bool sfm_ba_problem::kit_acquire() {
             ev_solve = k.ev_solve;
             h_ring = k.h_ring;
             d_ring = k.d_ring;
+            sk = k.sk;
             v.erase(v.begin() + i);
             return true;
         }
@@ -4524,6 +4610,60 @@ static int ba_create(int32_t nc, int64_t np_, int64_t no, const int32_t *cam, co
     p->gjp = p->tb == 16 && !p->gjrp.ok() ? gj_plan(p->nT, device_cus(device)) : GjPlan{};
     p->bs_cl_blocks = backsub_cl_blocks(nc, device_cus(device), p->pt_blocks);
     p->lin_cl_blocks = linearize_cl_blocks(nc, device_cus(device), p->pt_blocks);
+    // Speculation (one rank, a persistent solve): second copies of what the
+    // rejection branch's chain writes, and its sweep's dispatch on the CUs the
+    // solve's nT workgroups leave free.  Same lists, cuts and slots as the
+    // plan above: the items past the free CUs are cut into S chunk
+    // sub-ranges each (SweepSplit).  Every copy is written by the chain
+    // before anything reads it, like d_Lq / d_slab / d_payload themselves.
+    std::vector<int32_t> sp_split_of;  // (lives until the upload's stream sync below)
+    if (!p->comm && (p->gjrp.ok() || p->gjp.cb) && !sw.split_S && sw.nrange <= NXCD) {
+        const int ncu = device_cus(device);
+        const int nwg = p->gjrp.ok() ? p->gjrp.nT : p->gjp.grid();
+        // Workgroups go to the XCDs round-robin, the solve's as the sweep's, and
+        // an XCD's workgroup past its free CUs waits for one, a whole item's
+        // span: so NXCD times the free CUs of the fullest XCD, not ncu - nwg
+        // (cfg5: 8 x (32 - 10) = 176, not 181: with 181 three XCDs held 23
+        // whole items on 22 CUs and the sweep took 559 us instead of ~350)
+        const int free_cus = NXCD * std::max(0, ncu / NXCD - ceil_div(nwg, NXCD));
+        p->sp_free_cus = std::max(0, std::min(ncu, env_int("SFM_SPEC_FREE_CUS", free_cus)));
+        int32_t S = 0, nsplit = 0, gmax = 0;
+        const int items = sw.nspec * sw.nrange;
+        if (items > p->sp_free_cus) {
+            int min_chunks = INT32_MAX;
+            for (int r = 0; r < sw.nrange; ++r) min_chunks = std::min(min_chunks, sw.rchunk[r + 1] - sw.rchunk[r]);
+            S = std::min(8, min_chunks);
+            nsplit = std::min(sw.nspec, ceil_div(items - p->sp_free_cus, sw.nrange));
+            // whole items in equal numbers on every XCD (the kernel deals NXCD / nrange specs per round of NXCD)
+            if (sw.nrange < NXCD) nsplit = sw.nspec - (sw.nspec - nsplit) / (NXCD / sw.nrange) * (NXCD / sw.nrange);
+            if (S < 2) S = nsplit = 0;  // single-chunk ranges: the items run whole, in rounds
+        }
+        const int32_t w0 = sw.nspec - nsplit;
+        std::vector<int32_t> &split_of = sp_split_of;
+        split_of.assign(sw.nbd, -1);
+        for (int w = w0; S && w < sw.nspec; ++w) gmax = std::max(gmax, sw.goff[w + 1] - sw.goff[w]);
+        for (int w = w0; S && w < sw.nspec; ++w)
+            for (int g = sw.goff[w]; g < sw.goff[w + 1]; ++g)
+                split_of[sw.groups[g].blk] = (w - w0) * gmax + (g - sw.goff[w]);
+        const int32_t nfull = sw.nrange < NXCD ? NXCD * ceil_div(w0, NXCD / sw.nrange) : NXCD * w0;
+        p->sp_split = {nfull, S, w0, nsplit, gmax, nullptr};
+        if ((rc = p->alloc(p->d_sp_slab, (int64_t)ITEM_W * sw.nrange * sw.nbd)) ||
+            (rc = p->alloc(p->sp_split.slabx, std::max<int64_t>(1, (int64_t)ITEM_W * sw.nrange * S * nsplit * gmax))) ||
+            (rc = p->alloc(p->d_sp_split_of, split_of.size())) ||
+            (rc = p->alloc(p->d_sp_Lq[0], 9 * np_)) || (rc = p->alloc(p->d_sp_Lq[1], 9 * np_)) ||
+            (rc = p->alloc(p->d_sp_payload[0], p->payload_len + 8)) ||
+            (rc = p->alloc(p->d_sp_payload[1], p->payload_len + 8)))
+            return rc;
+        if (!split_of.empty())
+            SFM_HIP(hipMemcpyAsync(p->d_sp_split_of, split_of.data(), split_of.size() * 4, hipMemcpyHostToDevice, p->stream));
+        // the second stream with the problem's first (both stay with the StreamKit:
+        // a later create finds them made)
+        if ((rc = p->sk.make(false))) return rc;
+        p->spec_ok = true;
+        if (env_int("SFM_SWEEP_VERBOSE", 0))
+            std::fprintf(stderr, "speculative sweep: %d free CUs, %d whole items, %d specs x %d ranges cut into %d\n",
+                         p->sp_free_cus, w0 * sw.nrange, nsplit, sw.nrange, S);
+    }
     if (p->gjrp.ok()) {
         gjr::u64 *gw = nullptr;
         int *gi = nullptr;
@@ -4634,6 +4774,17 @@ static int ba_create(int32_t nc, int64_t np_, int64_t no, const int32_t *cam, co
 extern "C" int sfm_ba_plan_digest(sfm_ba_problem *p, uint64_t *out) {
     SFM_CHECK_ARG(p && out, "null pointer");
     *out = p->plan_digest;
+    return 0;
+}
+
+extern "C" int sfm_ba_spec_plan(sfm_ba_problem *p, int32_t out[4]) {
+    SFM_CHECK_ARG(p && out, "null pointer");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!p->spec_ok) return 0;
+    out[0] = p->sp_free_cus;
+    out[1] = p->sp_split.w0 * p->sw_nrange;
+    out[2] = p->sp_split.nsplit;
+    out[3] = p->sp_split.S;
     return 0;
 }
 
@@ -4887,19 +5038,65 @@ static int run_linearize(sfm_ba_problem *p, int par, int want_cost) {
     return want_cost ? allreduce(p, p->d_scal + 8, 1) : 0;
 }
 
+// The rejection branch's damped system, built on the second stream beside
+// iteration it's reduced solve: k_point_prep at lambda * nu, the sweep in its
+// free-CU dispatch (sp_split) without camera workgroups (the camera blocks
+// stand after a rejection), k_schur_finish, all into set it & 1 and gated on
+// the device's run_spec.  It reads V_p, X, the cameras and the camera blocks,
+// which nothing writes before k_lm_step (run_step joins the streams there).
+static int run_spec_chain(sfm_ba_problem *p, int par, int it, bool timed) {
+    hipStream_t s2 = p->sk.stream;
+    const int *gsp = &p->d_lm[par].run_spec;
+    const double *lam = &p->d_lm[par].spec_lambda;
+    double *Lq = p->d_sp_Lq[it & 1], *payload = p->d_sp_payload[it & 1];
+    hipEvent_t *tm = p->sk.tm + 4 * (it % kEvSlots);
+    if (timed) SFM_HIP(hipEventRecord(tm[0], s2));
+    hipLaunchKernelGGL(k_point_prep, dim3(std::max(1, ceil_div(p->np, OBS_THREADS))), dim3(OBS_THREADS), 0, s2,
+                       (int64_t)p->np, p->d_Vg, lam, Lq, gsp);
+    SFM_HIP(hipGetLastError());
+    if (timed) SFM_HIP(hipEventRecord(tm[1], s2));
+    if (timed) SFM_HIP(hipEventRecord(tm[2], s2));
+    const SweepSplit &sp = p->sp_split;
+    const int nsweep = sp.S                ? sp.nfull + p->sw_nrange * sp.nsplit * sp.S
+                       : p->sw_nrange < NXCD ? NXCD * ceil_div(p->sw_nspec, NXCD / p->sw_nrange)
+                                             : NXCD * p->sw_nspec * ceil_div(p->sw_nrange, NXCD);
+    auto sweep_k = p->sw_pinhole ? k_schur_sweep<1, true> : k_schur_sweep<1>;
+    hipLaunchKernelGGL(sweep_k, dim3(nsweep), dim3(SW_THREADS), p->sw_lds_bytes, s2, p->sw_nspec, p->sw_nrange,
+                       p->sw_nbd, p->sw_L, p->d_sw_rchunk, p->d_sw_nload, p->d_sw_goff, p->d_sw_groups,
+                       p->d_sw_lanegrp, p->d_sw_scam, reinterpret_cast<const uint32_t *>(p->d_sw_list), p->d_sw_pairs,
+                       p->d_sw_hdr, p->d_X, Lq, p->d_Rt, p->K, p->d_sp_slab, gsp, p->sw_debug, nsweep,
+                       camlin_args(p, true, &p->d_lm[par].run_lin), (long long *)nullptr, p->d_sw_err, sp);
+    SFM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_schur_finish, dim3(ceil_div(p->sw_nbd * ITEM_W, FIN_THREADS)), dim3(FIN_THREADS), 0, s2, p->ns,
+                       p->sw_nbd, p->sw_nrange, p->d_sw_blkij, p->d_sp_slab, p->d_camlin, payload, gsp,
+                       p->d_sp_split_of, sp);
+    SFM_HIP(hipGetLastError());
+    if (timed) SFM_HIP(hipEventRecord(tm[3], s2));
+    SFM_HIP(hipEventRecord(p->sk.join[it % kSpecRing], s2));
+    p->sp_queued[it % kEvSlots] = true;
+    return 0;
+}
+
 // one damped solve + trial evaluation (gated on the device LM state); leaves
 // d_scal = [cost_trial, model_p, dn_p, xn_p, model_c, dn_c, xn_c] and d_bad for
 // k_lm_step.  ev: this iteration's timing-event slot (nullable).
-static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par) {
+// it: the iteration (its speculative chain writes set it & 1, its solve and
+// trial may read set (it - 1) & 1).
+static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par, int it) {
     hipStream_t s = p->stream;
     int rc;
     const bool timed = ev != nullptr;
     const int *gst = &p->d_lm[par].run_step;
+    // this iteration's own prep / sweep / finish: off when its system was speculated
+    const int *greal = p->spec_on ? &p->d_lm[par].run_real : gst;
+    const int *use_spec = p->spec_on ? &p->d_lm[par].use_spec : nullptr;
+    const double *Lq_spec = p->spec_on ? p->d_sp_Lq[(it - 1) & 1] : nullptr;
+    const double *pay_spec = p->spec_on ? p->d_sp_payload[(it - 1) & 1] : nullptr;
     const double *lam = &p->d_lm[par].lambda;
     int *bad = p->d_bad + par;
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_PREP], s));
     hipLaunchKernelGGL(k_point_prep, dim3(std::max(1, ceil_div(p->np, OBS_THREADS))), dim3(OBS_THREADS), 0, s, (int64_t)p->np,
-                       p->d_Vg, lam, p->d_Lq, gst);
+                       p->d_Vg, lam, p->d_Lq, greal);
     SFM_HIP(hipGetLastError());
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_PREP + 1], s));
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_SCHUR], s));
@@ -4912,7 +5109,7 @@ static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par) {
                        p->sw_lds_bytes, s, p->sw_nspec, p->sw_nrange, p->sw_nbd, p->sw_L, p->d_sw_rchunk,
                        p->d_sw_nload, p->d_sw_goff, p->d_sw_groups, p->d_sw_lanegrp, p->d_sw_scam,
                        reinterpret_cast<const uint32_t *>(p->d_sw_list), p->d_sw_pairs, p->d_sw_hdr, p->d_X, p->d_Lq,
-                       p->d_Rt, p->K, p->d_slab, gst, p->sw_debug, nsweep,
+                       p->d_Rt, p->K, p->d_slab, greal, p->sw_debug, nsweep,
                        camlin_args(p, true, &p->d_lm[par].run_lin), sw_dbg_ptr(), p->d_sw_err, p->sw_split);
     SFM_HIP(hipGetLastError());
     // one rank: the solve's first launch sums the slabs itself (SlabSrc)
@@ -4923,13 +5120,19 @@ static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par) {
     const bool fin_fused = !p->comm && p->fin_fused && !p->gjp.cb && (!p->gjrp.ok() || p->gjr_fold);
     if (!fin_fused) {
         hipLaunchKernelGGL(k_schur_finish, dim3(ceil_div(p->sw_nbd * ITEM_W, FIN_THREADS)), dim3(FIN_THREADS), 0, s, p->ns, p->sw_nbd, p->sw_nrange,
-                           p->d_sw_blkij, p->d_slab, p->d_camlin, p->d_payload, gst, p->d_sw_split_of, p->sw_split);
+                           p->d_sw_blkij, p->d_slab, p->d_camlin, p->d_payload, greal, p->d_sw_split_of, p->sw_split);
         SFM_HIP(hipGetLastError());
     }
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_SCHUR + 1], s));
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_COMM], s));
     if ((rc = allreduce(p, p->d_payload, p->payload_len - 1))) return rc;
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_COMM + 1], s));
+    // the payload of this iteration's system is finished: the speculative
+    // chain may start with the solve
+    if (p->spec_armed) {
+        SFM_HIP(hipEventRecord(p->sk.fork[it % kSpecRing], s));
+        SFM_HIP(hipStreamWaitEvent(p->sk.stream, p->sk.fork[it % kSpecRing], 0));
+    }
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_SOLVE], s));
     // the back substitution's epilogue forms the trial cameras (k_camera_trial's work)
     const CamTrialArgs ct = {p->nc, p->ns, p->d_payload, lam, p->d_Rt, p->d_Rt2, p->d_scal + 4};
@@ -4944,11 +5147,13 @@ static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par) {
         }
         if (p->gjrp.ok()) {
             if ((rc = launch_gjr(p->gjrp, p->ns, p->d_payload, lam, p->gjrb, ++p->gjr_tag, p->d_b, bad, gst, ct, s,
-                                 src)))
+                                 src, pay_spec, use_spec)))
                 return rc;
         } else if ((rc = launch_gj(p->gjp, p->nT, p->ns, p->d_payload, lam, p->gjb, ++p->gj_epoch, p->d_b, bad,
-                                   gst, ct, s)))
+                                   gst, ct, s, pay_spec, use_spec)))
             return rc;
+        // the solve's workgroups are queued: now the speculative chain beside them
+        if (p->spec_armed && (rc = run_spec_chain(p, par, it, timed))) return rc;
         if (lg) {
             SFM_HIP(hipEventRecord(p->ev_solve, s));
             lg->last_solve = p->ev_solve;
@@ -4968,11 +5173,14 @@ static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par) {
     const size_t cl_lds = cl ? (size_t)8 * BS_CAM * p->nc : 0;
     hipLaunchKernelGGL((cl ? k_backsub_trial<BS_LANES, true, 256> : k_backsub_trial<BS_LANES, false>), dim3(nbb),
                        dim3(bst), cl_lds, s, p->np, p->nc, p->d_pstart, p->d_cam, p->d_obs, p->K, p->d_Vg, p->d_Lq,
-                       p->d_b, lam, p->d_Rt, p->d_Rt2, p->d_X, p->d_X2, p->d_partial, p->d_count + GS_WORDS, p->d_scal,
+                       Lq_spec, use_spec, p->d_b, lam, p->d_Rt, p->d_Rt2, p->d_X, p->d_X2, p->d_partial, p->d_count + GS_WORDS, p->d_scal,
                        gst);
     SFM_HIP(hipGetLastError());
     if ((rc = allreduce(p, p->d_scal, 4))) return rc;
     if (timed) SFM_HIP(hipEventRecord(ev[2 * T_TRIAL + 1], s));
+    // k_lm_step moves X and the cameras on, and the next linearisation V_p:
+    // the speculative chain read them
+    if (p->spec_armed) SFM_HIP(hipStreamWaitEvent(s, p->sk.join[it % kSpecRing], 0));
     return 0;
 }
 
@@ -5017,6 +5225,15 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
     p->chol_dpp = env_int("SFM_CHOL_DPP", 1) != 0;
     p->fin_fused = env_int("SFM_FINISH_FUSED", 1) != 0;
     p->gjr_fold = env_int("SFM_GJR_FOLD", 0) != 0;
+    // Speculation (SFM_SPECULATE=0: off): armed by this solve's first rejected
+    // step, so a solve whose steps are all accepted queues what it always
+    // did.  Not with gradient_tolerance (its check sits between the
+    // linearisation and the step) nor with the finish folded into the solve
+    // (the solve then reads the slabs, not a payload).
+    p->spec_on = p->spec_ok && env_int("SFM_SPECULATE", 1) != 0 && o->gradient_tolerance == 0.0 &&
+                 !(p->gjrp.ok() && p->gjr_fold);
+    p->spec_armed = false;
+    for (bool &q : p->sp_queued) q = false;
     (void)hipGetLastError();
     const auto t0 = std::chrono::steady_clock::now();
     for (double &t : p->t_acc) t = 0;
@@ -5047,6 +5264,13 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
             float ms = 0;
             if (hipEventElapsedTime(&ms, e[2 * k], e[2 * k + 1]) == hipSuccess) p->t_acc[k] += ms;
         }
+        if (p->sp_queued[j % kEvSlots]) {  // the speculative chain's share of the two phases
+            const hipEvent_t *tm = p->sk.tm + 4 * (j % kEvSlots);
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, tm[0], tm[1]) == hipSuccess) p->t_acc[T_PREP] += ms;
+            if (hipEventElapsedTime(&ms, tm[2], tm[3]) == hipSuccess) p->t_acc[T_SCHUR] += ms;
+            p->sp_queued[j % kEvSlots] = false;
+        }
         p->t_iters++;
     };
     const int64_t nacc = std::max<int64_t>(3 * p->np, 12 * (int64_t)p->nc);
@@ -5058,6 +5282,11 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
             const LMState &st = p->h_ring[j % kHostRing].st;
             if (timed && st.iters == j + 1) account(j);
             if (st.done) break;
+            // a rejection was published: from here on every iteration carries the chain
+            if (p->spec_on && !p->spec_armed && st.armed) {
+                if ((rc = p->sk.make(timed))) return rc;
+                p->spec_armed = true;
+            }
         }
         hipEvent_t *ev = timed ? p->ev_it + (size_t)(it % kEvSlots) * 2 * T_NT : nullptr;
         if (timed) SFM_HIP(hipEventRecord(ev[2 * T_LIN], s));
@@ -5077,13 +5306,13 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
                                p->d_lm + par, glin);
             SFM_HIP(hipGetLastError());
         }
-        if ((rc = run_step(p, ev, par))) return rc;
+        if ((rc = run_step(p, ev, par, it))) return rc;
         // bounded grid, grid-stride copy: after a rejected step nothing is copied
         hipLaunchKernelGGL(k_lm_step, dim3(std::min(ceil_div(nacc, 256), 512)), dim3(256), 0, s, p->d_lm + par,
                            p->d_lm + (par ^ 1),
                            p->d_scal, p->d_bad + par, p->d_bad + (par ^ 1), o->max_iterations, o->fixed_iterations,
                            o->function_tolerance, o->parameter_tolerance, o->initial_lambda, p->np, p->nc, p->d_X,
-                           p->d_X2, p->d_Rt, p->d_Rt2, p->d_ring, it + 1);
+                           p->d_X2, p->d_Rt, p->d_Rt2, p->d_ring, it + 1, (p->spec_on ? 1 : 0) | (p->spec_armed ? 2 : 0));
         SFM_HIP(hipGetLastError());
     }
     // the iterations still in flight (gated off if the solve ended earlier)

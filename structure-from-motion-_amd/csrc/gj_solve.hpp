@@ -73,6 +73,10 @@ struct Args {
     unsigned *arrive;  // last-block arrivals (the last one runs the epilogue)
     CamTrialArgs ct;   // trial cameras epilogue (nc = 0: none)
     long long *dbg;    // diagnostics (nullable): [grid][nT][16] s_memrealtime stamps
+    // the payload speculated beside the last solve, taken instead of `payload`
+    // when *use_spec (device LM state; nullable: never)
+    const double *payload_spec = nullptr;
+    const int *use_spec = nullptr;
 };
 
 // diagnostic stamps (sfm_gj_debug): slot per (workgroup, panel)
@@ -740,6 +744,7 @@ __device__ __forceinline__ void final_solve(const double *Lp, double *x, int nse
 
 __global__ void __launch_bounds__(THREADS) k_gj_solve(Args a) {
     if (a.gate && !*a.gate) return;  // device-side LM control: iteration gated off
+    if (a.use_spec && *a.use_spec) a.payload = a.payload_spec;  // the system speculated beside the last solve
     __shared__ Smem S;
     stamp(a, a.nT, DBG_START);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -82,6 +82,10 @@ struct Args {
     unsigned *arrive;
     CamTrialArgs ct;  // trial cameras epilogue (nc = 0: none)
     long long *dbg;   // diagnostics (nullable): [grid][nT + 1][16] s_memrealtime stamps
+    // the payload speculated beside the last solve, taken instead of `payload`
+    // when *use_spec (device LM state; nullable: never)
+    const double *payload_spec = nullptr;
+    const int *use_spec = nullptr;
 };
 
 enum { DBG_PIN = 0, DBG_GCRIT, DBG_CHAIN0, DBG_CHAIN1, DBG_PPUB, DBG_GHOLD, DBG_UDONE, DBG_GREM, DBG_PLW, DBG_GRDY, DBG_HPRDY };
@@ -719,6 +723,7 @@ __device__ __forceinline__ bool u_loop(const Args &a, const Rs &rs, Smem &S, int
 template <int TR, int TLS>
 __global__ void __launch_bounds__(THREADS) k_gjr_solve(Args a) {
     if (a.gate && !*a.gate) return;  // device-side LM control: iteration gated off
+    if (a.use_spec && *a.use_spec) a.payload = a.payload_spec;  // the system speculated beside the last solve
     __shared__ Smem S;
     extern __shared__ __attribute__((aligned(16))) double dyn[];  // LDS tile slots, then the epilogue's scratch
     static_assert(NUW * TLS * 256 * sizeof(double) <= DYN_LDS, "LDS tile slots");
