@@ -732,6 +732,56 @@ int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const int64_t *img_
                           int32_t *match_dsq, int32_t *nn, int32_t *d1, int32_t *d2, int32_t *nn_rev, int device);
 
 /* ---------------------------------------------------------------------
+ * Guided descriptor matching: sfm_match_descriptors with the candidates of a
+ * keypoint restricted to a band around its epipolar line.  The stage behind
+ * pair verification: with a trusted F per pair, the matches that the ratio
+ * test and the cross-check lose to repeated structure come back.
+ * The arguments of sfm_match_descriptors and: xy, n_kp x 2 fp64 keypoint
+ * coordinates in desc's row order; F, P x 9 fp64 row-major, one matrix per
+ * pair in sfm_verify_pairs' convention x_j^T F x_i = 0 for the pair (i, j)
+ * -- (x, y) is the keypoint of the first image of the pair, (u, v) of the
+ * second, and a caller who lists the pair as (j, i) passes F^T; gate, the
+ * half-width of the band in pixels, finite and >= 0.
+ * Definitions, from which every output follows:
+ *   thr2 = gate * gate, one fp64 product; it may overflow to +inf, which is
+ *     defined: every pair of keypoints with den > 0 then passes;
+ *   gate_p(a, b) for keypoint a = (x, y) of i and b = (u, v) of j under
+ *     F = F_p, fp64 with no contraction, in this order of operations:
+ *       l0 = (F0 x + F1 y) + F2, l1 = (F3 x + F4 y) + F5, l2 = (F6 x + F7 y) + F8,
+ *       m0 = (F0 u + F3 v) + F6, m1 = (F1 u + F4 v) + F7,
+ *       e = (u l0 + v l1) + l2, den = (l0 l0 + l1 l1) + (m0 m0 + m1 m1),
+ *       gate_p = den > 0 && e e < thr2 den
+ *     -- the squared Sampson distance against the squared half-width, the
+ *     inlier rule of sfm_verify_pairs bit for bit; false for anything not
+ *     finite, so a pair whose F holds a NaN (what sfm_verify_pairs returns for
+ *     a failed pair) has no candidates and no matches, which is not an error;
+ *   the candidates of a: C(a) = { b in j : gate_p(a, b) }, n_cand[a] = |C(a)|;
+ *   nn, d1, d2: sfm_match_descriptors' with the (dsq, local index) order taken
+ *     over C(a) only; d2 = INT32_MAX when |C(a)| < 2, nn = -1 and
+ *     d1 = INT32_MAX when C(a) is empty;
+ *   nn_rev[b]: the first of the same order over { a in i : gate_p(a, b) } --
+ *     the same predicate with the same argument roles and the same bits, no
+ *     transposed matrix, so a pair of keypoints is a candidate in both
+ *     directions or in neither;
+ *   acceptance (max_dsq, the ratio test on the forward direction only,
+ *     cross_check), compaction, the capacity bound, the pair-major order and
+ *     ascending a inside a pair are sfm_match_descriptors'.
+ * Outputs as sfm_match_descriptors'; n_cand is one more nullable diagnostic,
+ * pair-major like nn (sum of N_i entries).
+ * SFM_ERR_ARG, found on the host before a device is looked for, with nothing
+ * written: everything sfm_match_descriptors refuses; a null xy with n_kp > 0;
+ * a null F with P > 0; gate negative or not finite.  P == 0 succeeds without
+ * a device.
+ * Every output is the same from run to run.
+ * sfm_last_timings: upload, kernels, download.
+ * ------------------------------------------------------------------- */
+int sfm_match_descriptors_guided(const uint8_t *desc, const double *xy, int64_t n_kp, const int64_t *img_start,
+                                 int32_t n_images, int32_t dim, const int32_t *pairs, const double *F, int64_t P,
+                                 double gate, double ratio, int32_t max_dsq, int32_t cross_check, int64_t capacity,
+                                 int64_t *match_start, int32_t *match_a, int32_t *match_b, int32_t *match_dsq,
+                                 int32_t *nn, int32_t *d1, int32_t *d2, int32_t *nn_rev, int32_t *n_cand, int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

@@ -119,6 +119,9 @@ SIGNATURES = [
     ("sfm_match_descriptors", _c, [_u8, _i, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _i, ctypes.c_double,
                                    ctypes.c_int32, ctypes.c_int32, _i, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                    _c]),
+    ("sfm_match_descriptors_guided", _c, [_u8, _d, _i, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _d, _i,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _i, _i64,
+                                          _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -1165,14 +1168,27 @@ def match_descriptors(desc, img_start, pairs, ratio=0.8, max_dsq=INT32_MAX, cros
     and, with want_diagnostics, nn, d1, d2 (sum of N_i,) and nn_rev (sum of
     N_j,) int32, pair-major.  The arguments are checked before a device is
     looked for (SfmCoreError, nothing written); P == 0 needs no device."""
+    desc, st, pairs, capacity, outs, diag = _match_arrays("match_descriptors", desc, img_start, pairs, cross_check,
+                                                          capacity, want_diagnostics, "iiij")
+    _check(_lib.sfm_match_descriptors(_p(desc, _u8), len(desc), _p(st, _i64), len(st) - 1, desc.shape[1],
+                                      _p(pairs, _i32), len(pairs), float(ratio), int(max_dsq), int(bool(cross_check)),
+                                      capacity, _p(outs[0], _i64), *(_p(o, _i32) for o in outs[1:]),
+                                      *(None if d is None else _p(d, _i32) for d in diag), DEVICE))
+    return _match_result(outs, diag, ("nn", "d1", "d2", "nn_rev"), want_diagnostics)
+
+
+def _match_arrays(name, desc, img_start, pairs, cross_check, capacity, want_diagnostics, diag_sides):
+    """The inputs of a matching call as contiguous arrays, the capacity (default
+    the bound) and the caller-allocated outputs: (match_start, a, b, dsq) and one
+    diagnostic per letter of ``diag_sides`` -- "i": sum of N_i entries, "j": sum
+    of N_j -- or None without want_diagnostics."""
     desc = np.ascontiguousarray(desc, dtype=np.uint8)
     if desc.ndim != 2:
-        raise ValueError("match_descriptors: desc must be (n_kp, dim)")
+        raise ValueError(f"{name}: desc must be (n_kp, dim)")
     st = np.ascontiguousarray(img_start, dtype=np.int64).reshape(-1)
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
     if len(st) < 1:
-        raise ValueError("match_descriptors: img_start needs n_images + 1 entries")
-    n_kp, dim = desc.shape
+        raise ValueError(f"{name}: img_start needs n_images + 1 entries")
     n_images, P = len(st) - 1, len(pairs)
     n = np.diff(st)
     inside = bool(P == 0 or (pairs.min() >= 0 and pairs.max() < n_images))
@@ -1182,18 +1198,54 @@ def match_descriptors(desc, img_start, pairs, ratio=0.8, max_dsq=INT32_MAX, cros
     capacity = max(bound, 0) if capacity is None else int(capacity)
     match_start = np.zeros(P + 1, dtype=np.int64)
     a, b, dsq = (np.full(max(capacity, 0), -1, dtype=np.int32) for _ in range(3))
-    diag = [None] * 4
+    diag = [None] * len(diag_sides)
     if want_diagnostics:
-        diag = [np.full(max(int(k.sum()), 0), -1, dtype=np.int32) for k in (ni, ni, ni, nj)]
-    _check(_lib.sfm_match_descriptors(_p(desc, _u8), n_kp, _p(st, _i64), n_images, dim, _p(pairs, _i32), P,
-                                      float(ratio), int(max_dsq), int(bool(cross_check)), capacity,
-                                      _p(match_start, _i64), _p(a, _i32), _p(b, _i32), _p(dsq, _i32),
-                                      *(None if d is None else _p(d, _i32) for d in diag), DEVICE))
+        diag = [np.full(max(int((ni if k == "i" else nj).sum()), 0), -1, dtype=np.int32) for k in diag_sides]
+    return desc, st, pairs, capacity, (match_start, a, b, dsq), diag
+
+
+def _match_result(outs, diag, names, want_diagnostics):
+    match_start, a, b, dsq = outs
     m = int(match_start[-1])
     out = dict(match_start=match_start, a=a[:m].copy(), b=b[:m].copy(), dsq=dsq[:m].copy())
     if want_diagnostics:
-        out.update(nn=diag[0], d1=diag[1], d2=diag[2], nn_rev=diag[3])
+        out.update(zip(names, diag))
     return out
+
+
+def match_descriptors_guided(desc, xy, img_start, pairs, F, gate, ratio=0.8, max_dsq=INT32_MAX, cross_check=True,
+                             capacity=None, want_diagnostics=False):
+    """Guided descriptor matching (sfm_match_descriptors_guided):
+    ``match_descriptors`` with the candidates of keypoint a of image i
+    restricted to the keypoints b of j inside the band of half-width ``gate``
+    pixels around a's epipolar line.  xy (n_kp, 2) are the keypoints in desc's
+    row order; F (P, 3, 3), one matrix per pair with x_j^T F x_i = 0 for the
+    pair (i, j) -- verify_pairs' convention; a pair listed as (j, i) takes
+    F^T.  A pair of keypoints is a candidate when den > 0 and
+    e^2 < (gate * gate) den, the squared Sampson distance of verify_pairs'
+    inlier rule, bit for bit (include/sfmcore.h has the operation order); it is
+    the same decision in the reverse pass of the cross-check.  An F with a NaN
+    gives a pair without candidates and without matches.  nn, d1, d2 and nn_rev
+    are taken over the candidates only (nn = -1 and d1 = INT32_MAX without one,
+    d2 = INT32_MAX with fewer than two); the tests, the capacity and the layout
+    are ``match_descriptors``'s.  Returns its dict; with want_diagnostics also
+    n_cand (sum of N_i,) int32, the number of candidates of each keypoint.
+    The arguments are checked before a device is looked for; P == 0 needs no
+    device."""
+    desc, st, pairs, capacity, outs, diag = _match_arrays("match_descriptors_guided", desc, img_start, pairs,
+                                                          cross_check, capacity, want_diagnostics, "iiiji")
+    xy = _f64(xy)
+    if xy.shape != (len(desc), 2):
+        raise ValueError("match_descriptors_guided: xy must be (n_kp, 2)")
+    F = _f64(F)
+    if F.shape != (len(pairs), 3, 3):
+        raise ValueError("match_descriptors_guided: F must be (P, 3, 3)")
+    _check(_lib.sfm_match_descriptors_guided(_p(desc, _u8), _p(xy), len(desc), _p(st, _i64), len(st) - 1,
+                                             desc.shape[1], _p(pairs, _i32), _p(F), len(pairs), float(gate),
+                                             float(ratio), int(max_dsq), int(bool(cross_check)), capacity,
+                                             _p(outs[0], _i64), *(_p(o, _i32) for o in outs[1:]),
+                                             *(None if d is None else _p(d, _i32) for d in diag), DEVICE))
+    return _match_result(outs, diag, ("nn", "d1", "d2", "nn_rev", "n_cand"), want_diagnostics)
 
 
 def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,

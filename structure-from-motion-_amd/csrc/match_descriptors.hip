@@ -38,64 +38,9 @@
 //   k_md_write   match_start and the compacted matches.
 //
 // Integer minima and a scan: every output is the same from run to run.
-#include <climits>
-#include <cmath>
-#include <vector>
-
-#include <rocprim/device/device_scan.hpp>
-
-#include "staging.hpp"
+#include "match_common.hpp"
 
 namespace sfm {
-
-constexpr int MD_THREADS = 256;
-constexpr int MD_WAVES = 4;
-constexpr int MD_MS = 2;                       // 16-row subtiles per wave
-constexpr int MD_BM = MD_WAVES * MD_MS * 16;   // rows of a workgroup
-constexpr int MD_TN = 64;                      // columns of an LDS tile
-constexpr int MD_PAD = 16;                     // bytes after each LDS row
-constexpr int32_t MD_NONE = INT32_MAX;
-constexpr int32_t MD_OUTSIDE = INT32_MAX - (1 << 24);  // norm of a column past the end: w stays >= 2^30
-constexpr int32_t MD_VALID = 1 << 30;                  // every real w is far below
-constexpr int64_t MD_MAX_KP = (int64_t)1 << 20;
-
-typedef int md_v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int md_sq4(uint32_t v) {  // sum of squares of four signed bytes
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int b = (int)(int8_t)(v >> (8 * k));
-        s += b * b;
-    }
-    return s;
-}
-
-// norm[kp] = || desc[kp] - 128 ||^2; DIM / 16 threads per keypoint
-template <int DIM>
-__global__ __launch_bounds__(MD_THREADS) void k_md_norms(const uint8_t *desc, int64_t n_kp, int32_t *norm) {
-    constexpr int CH = DIM / 16;
-    const int64_t g = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
-    const int64_t kp = g / CH;
-    int s = 0;
-    if (kp < n_kp) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(desc + g * 16);
-        s = md_sq4(v.x ^ 0x80808080u) + md_sq4(v.y ^ 0x80808080u) + md_sq4(v.z ^ 0x80808080u) +
-            md_sq4(v.w ^ 0x80808080u);
-    }
-#pragma unroll
-    for (int o = 1; o < CH; o <<= 1) s += __shfl_xor(s, o);
-    if (kp < n_kp && g % CH == 0) norm[kp] = s;
-}
-
-// merge the running (m1, i1, m2) of another lane into this one's, by (w, column)
-__device__ __forceinline__ void md_merge(int32_t &m1, int32_t &i1, int32_t &m2, int32_t om1, int32_t oi1, int32_t om2) {
-    const bool other = om1 < m1 || (om1 == m1 && oi1 < i1);
-    const int32_t lo2 = other ? om2 : m2, hi1 = other ? m1 : om1;
-    m2 = lo2 < hi1 ? lo2 : hi1;
-    m1 = other ? om1 : m1;
-    i1 = other ? oi1 : i1;
-}
 
 // pairs is (first, second) per pair when !SWAP and read as (second, first) when
 // SWAP; row_off[p] is where the pair's rows start in nn / d1 / d2.
@@ -237,49 +182,6 @@ __global__ __launch_bounds__(MD_THREADS) void k_md_nn(const uint8_t *__restrict_
     }
 }
 
-// flag[row_off[p] + a] = 1 when keypoint a of the pair's first image is matched
-__global__ __launch_bounds__(MD_THREADS) void k_md_accept(const int64_t *img_start, const int32_t *pairs, int64_t P,
-                                                          const int64_t *row_off, const int64_t *col_off,
-                                                          const int32_t *nn, const int32_t *d1, const int32_t *d2,
-                                                          const int32_t *nn_rev, double ratio_sq, int32_t max_dsq,
-                                                          int32_t *flag) {
-    for (int64_t p = blockIdx.y; p < P; p += gridDim.y) {
-        const int32_t ii = pairs[2 * p];
-        const int32_t ni = (int32_t)(img_start[ii + 1] - img_start[ii]);
-        const int32_t a = (int32_t)blockIdx.x * MD_THREADS + threadIdx.x;
-        if (a >= ni) continue;
-        const int64_t o = row_off[p] + a;
-        const int32_t b = nn[o], e1 = d1[o], e2 = d2[o];
-        bool ok = b >= 0 && e1 <= max_dsq;
-        ok = ok && (e2 == MD_NONE || (double)e1 < ratio_sq * (double)e2);
-        ok = ok && (!nn_rev || nn_rev[col_off[p] + b] == a);
-        flag[o] = ok ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(MD_THREADS) void k_md_write(const int64_t *img_start, const int32_t *pairs, int64_t P,
-                                                         const int64_t *row_off, const int32_t *nn, const int32_t *d1,
-                                                         const int32_t *flag, const int64_t *place,
-                                                         int64_t *match_start, int32_t *match_a, int32_t *match_b,
-                                                         int32_t *match_dsq) {
-    for (int64_t p = blockIdx.y; p < P; p += gridDim.y) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            match_start[p] = place[row_off[p]];
-            if (p == P - 1) match_start[P] = place[row_off[P]];
-        }
-        const int32_t ii = pairs[2 * p];
-        const int32_t ni = (int32_t)(img_start[ii + 1] - img_start[ii]);
-        const int32_t a = (int32_t)blockIdx.x * MD_THREADS + threadIdx.x;
-        if (a >= ni) continue;
-        const int64_t o = row_off[p] + a;
-        if (!flag[o]) continue;
-        const int64_t m = place[o];
-        match_a[m] = a;
-        match_b[m] = nn[o];
-        match_dsq[m] = d1[o];
-    }
-}
-
 }  // namespace sfm
 
 using namespace sfm;
@@ -289,34 +191,11 @@ extern "C" int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const in
                                      int32_t cross_check, int64_t capacity, int64_t *match_start, int32_t *match_a,
                                      int32_t *match_b, int32_t *match_dsq, int32_t *nn, int32_t *d1, int32_t *d2,
                                      int32_t *nn_rev, int device) {
-    SFM_CHECK_ARG(n_kp >= 0 && n_images >= 0 && P >= 0 && capacity >= 0, "n_kp, n_images, P or capacity < 0");
-    SFM_CHECK_ARG(dim == 64 || dim == 128 || dim == 256, "dim is not 64, 128 or 256");
-    SFM_CHECK_ARG(std::isfinite(ratio) && ratio > 0.0 && ratio <= 1.0, "ratio outside (0, 1]");
-    SFM_CHECK_ARG(max_dsq >= 0, "max_dsq < 0");
-    SFM_CHECK_ARG(cross_check == 0 || cross_check == 1, "cross_check is not 0 or 1");
-    SFM_CHECK_ARG(img_start && match_start, "null pointer");
-    SFM_CHECK_ARG(n_kp == 0 || desc, "null pointer");
-    SFM_CHECK_ARG(P == 0 || pairs, "null pointer");
-    SFM_CHECK_ARG(capacity == 0 || (match_a && match_b && match_dsq), "null pointer");
-    SFM_TRY(check_csr(img_start, n_images, n_kp, "img_start", "keypoint", MD_MAX_KP,
-                      "an image with more than 2^20 keypoints"));
-    // the pairs' extents in the pair-major arrays, and the bound on the matches
-    std::vector<int64_t> off(2 * (size_t)(P + 1));
-    int64_t *row_off = off.data(), *col_off = off.data() + (P + 1);
-    int64_t bound = 0, max_i = 0, max_j = 0;
-    row_off[0] = col_off[0] = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
-        SFM_CHECK_ARG(i >= 0 && i < n_images && j >= 0 && j < n_images, "a pair image outside [0, n_images)");
-        SFM_CHECK_ARG(i != j, "a pair of an image with itself");
-        const int64_t ni = img_start[i + 1] - img_start[i], nj = img_start[j + 1] - img_start[j];
-        row_off[p + 1] = row_off[p] + ni;
-        col_off[p + 1] = col_off[p] + nj;
-        bound += cross_check && nj < ni ? nj : ni;
-        if (ni > max_i) max_i = ni;
-        if (nj > max_j) max_j = nj;
-    }
-    SFM_CHECK_ARG(capacity >= bound, "capacity below the sum over the pairs of N_i (of min(N_i, N_j) with cross_check)");
+    MdPlan plan;
+    SFM_TRY(md_plan(desc, n_kp, img_start, n_images, dim, pairs, P, ratio, max_dsq, cross_check, capacity, match_start,
+                    match_a, match_b, match_dsq, plan));
+    const int64_t *row_off = plan.row_off(), *col_off = plan.col_off();
+    const int64_t max_i = plan.max_i, max_j = plan.max_j;
     const double ratio_sq = ratio * ratio;
 
     match_start[0] = 0;
@@ -328,8 +207,7 @@ extern "C" int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const in
     if (!c) return SFM_ERR_HIP;
     hipStream_t s = c->stream;
     size_t tmp_bytes = 0;
-    SFM_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, (int32_t *)nullptr, (int64_t *)nullptr, (int64_t)0,
-                                    (size_t)n_rows + 1, rocprim::plus<int64_t>(), s));
+    SFM_TRY(md_scan_bytes(n_rows, s, tmp_bytes));
 
     Pack in(c->buf[0]), out(c->buf[1]), work(c->buf[2]);
     const auto i_desc = in.add<uint8_t>(n_kp * dim);
@@ -357,29 +235,13 @@ extern "C" int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const in
     SFM_TRY(in.upload(i_co, col_off, s));
     SFM_TRY(tm.mark(s));
 
-    const dim3 T(MD_THREADS);
     const unsigned gy = (unsigned)(P < 65535 ? P : 65535);
     const uint8_t *d_desc = in.ptr(i_desc);
     const int64_t *d_is = in.ptr(i_is), *d_ro = in.ptr(i_ro), *d_co = in.ptr(i_co);
     const int32_t *d_pairs = in.ptr(i_pairs);
-    int32_t *d_norm = work.ptr(w_norm), *d_flag = work.ptr(w_flag);
+    int32_t *d_norm = work.ptr(w_norm);
     int32_t *d_nn = out.ptr(o_nn), *d_d1 = out.ptr(o_d1), *d_d2 = out.ptr(o_d2);
     int32_t *d_rev = reverse ? out.ptr(o_rev) : nullptr;
-#define MD_LAUNCH(kernel, grid, ...)                            \
-    do {                                                        \
-        hipLaunchKernelGGL(kernel, grid, T, 0, s, __VA_ARGS__); \
-        SFM_HIP(hipGetLastError());                             \
-    } while (0)
-#define MD_BY_DIM(launch)     \
-    do {                      \
-        if (dim == 64) {      \
-            launch(64);       \
-        } else if (dim == 128) { \
-            launch(128);      \
-        } else {              \
-            launch(256);      \
-        }                     \
-    } while (0)
     if (n_kp > 0) {
         const dim3 g_norm((unsigned)ceil_div(n_kp * (dim / 16), MD_THREADS));
 #define MD_NORMS(D) MD_LAUNCH(k_md_norms<D>, g_norm, d_desc, n_kp, d_norm)
@@ -400,18 +262,10 @@ extern "C" int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const in
         MD_BY_DIM(MD_REV);
 #undef MD_REV
     }
-    const dim3 g_rows((unsigned)(max_i > 0 ? ceil_div(max_i, MD_THREADS) : 1), gy);
-    SFM_HIP(hipMemsetAsync(d_flag + n_rows, 0, sizeof(int32_t), s));
-    if (max_i > 0)
-        MD_LAUNCH(k_md_accept, g_rows, d_is, d_pairs, P, d_ro, d_co, d_nn, d_d1, d_d2,
-                  cross_check ? (const int32_t *)d_rev : (const int32_t *)nullptr, ratio_sq, max_dsq, d_flag);
-    size_t tb = tmp_bytes;
-    SFM_HIP(rocprim::exclusive_scan(work.ptr(w_tmp), tb, d_flag, work.ptr(w_place), (int64_t)0, (size_t)n_rows + 1,
-                                    rocprim::plus<int64_t>(), s));
-    MD_LAUNCH(k_md_write, g_rows, d_is, d_pairs, P, d_ro, d_nn, d_d1, d_flag, work.ptr(w_place), out.ptr(o_ms),
-              out.ptr(o_a), out.ptr(o_b), out.ptr(o_dsq));
-#undef MD_BY_DIM
-#undef MD_LAUNCH
+    SFM_TRY(md_compact(s, P, max_i, n_rows, d_is, d_pairs, d_ro, d_co, d_nn, d_d1, d_d2,
+                       cross_check ? (const int32_t *)d_rev : (const int32_t *)nullptr, ratio_sq, max_dsq,
+                       work.ptr(w_flag), work.ptr(w_place), work.ptr(w_tmp), tmp_bytes, out.ptr(o_ms), out.ptr(o_a),
+                       out.ptr(o_b), out.ptr(o_dsq)));
     SFM_TRY(tm.mark(s));
 
     // match_start first: its last entry sizes the other copies

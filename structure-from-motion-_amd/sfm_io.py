@@ -267,44 +267,83 @@ def match_descriptors(keypoints, descriptors, pairs=None, ratio=0.8, max_distanc
     (i, keypoints[i][a]) and (j, keypoints[j][b]), images ascending inside the
     row, read_matching's dtypes and zero flags, so store.merge_tracks() joins
     the matches into tracks and verify_pairs accepts either store."""
+    kps, desc, img_start, pair_ij, max_dsq = _match_inputs("match_descriptors", keypoints, descriptors, pairs, ratio,
+                                                           max_distance)
+    out = _core.match_descriptors(desc, img_start, pair_ij, ratio, max_dsq, cross_check)
+    store = match_store(kps, pair_ij, out["match_start"], out["a"], out["b"])
+    return store, pair_ij, out["match_start"], out["a"], out["b"], out["dsq"]
+
+
+def match_descriptors_guided(keypoints, descriptors, pairs, F, threshold=4.0, ratio=0.8, max_distance=None,
+                             cross_check=True):
+    """``match_descriptors`` guided by the pairs' epipolar geometry
+    (sfm_match_descriptors_guided): keypoint a of image i is compared only with
+    the keypoints of j whose Sampson distance to it under the pair's F is below
+    ``threshold`` pixels -- verify_pairs' inlier rule, bit for bit -- and the
+    nearest, the second nearest, the ratio test and the cross-check are taken
+    over those candidates alone.  Matches that the unguided call loses to
+    repeated structure, where two near-identical descriptors in j fail the
+    ratio test although only one lies near the epipolar line, come back.
+    ``pairs`` (P, 2) is required and ``F`` is (P, 3, 3) with
+    x_j^T F x_i = 0 for the pair (i, j), the convention of verify_pairs; a pair
+    listed as (j, i) takes F^T.  A pair whose F is not finite (verify_pairs'
+    failed pairs) gets no matches.  ``threshold`` must be finite and >= 0.
+    Everything else, and the returned (store, pair_ij, match_start, a, b, dsq),
+    are ``match_descriptors``'s, so store.merge_tracks() and verify_pairs accept
+    the result unchanged."""
+    kps, desc, img_start, pair_ij, max_dsq = _match_inputs("match_descriptors_guided", keypoints, descriptors, pairs,
+                                                           ratio, max_distance)
+    F = np.asarray(F, dtype=np.float64)
+    if F.shape != (len(pair_ij), 3, 3):
+        raise ValueError("match_descriptors_guided: F must be (P, 3, 3), one matrix per pair")
+    if not (np.isfinite(threshold) and threshold >= 0):
+        raise ValueError("match_descriptors_guided: threshold must be finite and >= 0")
+    xy = np.concatenate([np.zeros((0, 2))] + kps)
+    out = _core.match_descriptors_guided(desc, xy, img_start, pair_ij, F, float(threshold), ratio, max_dsq,
+                                         cross_check)
+    store = match_store(kps, pair_ij, out["match_start"], out["a"], out["b"])
+    return store, pair_ij, out["match_start"], out["a"], out["b"], out["dsq"]
+
+
+def _match_inputs(name, keypoints, descriptors, pairs, ratio, max_distance):
+    """The input checks that the matching calls share.  Returns (keypoints as
+    fp64 arrays, desc, img_start, pair_ij, max_dsq)."""
     import itertools
     if len(keypoints) != len(descriptors):
-        raise ValueError("match_descriptors: keypoints and descriptors need one entry per image")
+        raise ValueError(f"{name}: keypoints and descriptors need one entry per image")
     n_images = len(keypoints)
     kps, descs = [], []
     for k in range(n_images):
         d = np.asarray(descriptors[k])
         if d.dtype != np.uint8 or d.ndim != 2:
-            raise ValueError("match_descriptors: descriptors[k] must be (N_k, dim) uint8")
+            raise ValueError(f"{name}: descriptors[k] must be (N_k, dim) uint8")
         if descs and d.shape[1] != descs[0].shape[1]:
-            raise ValueError("match_descriptors: the descriptors differ in length")
+            raise ValueError(f"{name}: the descriptors differ in length")
         kp = np.asarray(keypoints[k], dtype=np.float64)
         if kp.shape != (len(d), 2):
-            raise ValueError("match_descriptors: keypoints[k] must be (N_k, 2) with one row per descriptor")
+            raise ValueError(f"{name}: keypoints[k] must be (N_k, 2) with one row per descriptor")
         if not np.isfinite(kp).all():
-            raise ValueError("match_descriptors: a keypoint coordinate is not finite")
+            raise ValueError(f"{name}: a keypoint coordinate is not finite")
         kps.append(kp)
         descs.append(d)
     if n_images and descs[0].shape[1] not in (64, 128, 256):
-        raise ValueError("match_descriptors: the descriptor length must be 64, 128 or 256")
+        raise ValueError(f"{name}: the descriptor length must be 64, 128 or 256")
     if pairs is None:
         pairs = list(itertools.combinations(range(n_images), 2))
     pair_ij = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     if len(pair_ij) and (pair_ij.min() < 0 or pair_ij.max() >= n_images or np.any(pair_ij[:, 0] == pair_ij[:, 1])):
-        raise ValueError("match_descriptors: pairs must be (i, j) with i != j in [0, n_images)")
+        raise ValueError(f"{name}: pairs must be (i, j) with i != j in [0, n_images)")
     if not (np.isfinite(ratio) and 0.0 < ratio <= 1.0):
-        raise ValueError("match_descriptors: ratio must be in (0, 1]")
+        raise ValueError(f"{name}: ratio must be in (0, 1]")
     max_dsq = _core.INT32_MAX
     if max_distance is not None:
         if not (np.isfinite(max_distance) and max_distance >= 0):
-            raise ValueError("match_descriptors: max_distance must be finite and >= 0")
+            raise ValueError(f"{name}: max_distance must be finite and >= 0")
         max_dsq = int(min(np.floor(float(max_distance) ** 2), _core.INT32_MAX))
     dim = descs[0].shape[1] if n_images else 128
     desc = np.concatenate([np.zeros((0, dim), dtype=np.uint8)] + descs)
     img_start = np.concatenate([[0], np.cumsum([len(d) for d in descs])]).astype(np.int64)
-    out = _core.match_descriptors(desc, img_start, pair_ij, ratio, max_dsq, cross_check)
-    store = match_store(kps, pair_ij, out["match_start"], out["a"], out["b"])
-    return store, pair_ij, out["match_start"], out["a"], out["b"], out["dsq"]
+    return kps, desc, img_start, pair_ij, max_dsq
 
 
 def read_matching(data_path, no_of_images, n_threads=0):

@@ -29,6 +29,7 @@ import numpy as np
 import _sfmcore as _core
 from sfm_io import merge_tracks  # noqa: F401  (the stage list's first entry lives with the store)
 from sfm_io import match_descriptors  # noqa: F401  (in front of it: descriptors to a store)
+from sfm_io import match_descriptors_guided  # noqa: F401  (behind verify_pairs: rematch_verified)
 from sfm_two_view import projection
 
 
@@ -175,6 +176,30 @@ def verify_pairs_calibrated(store, K, images=None, H=256, seed=0, threshold=2.5,
         store.flag[index1[ok]] = 1
         store.flag[index2[ok]] = 1
     return order, pair_ij, out, index1, index2
+
+
+def rematch_verified(keypoints, descriptors, verified, threshold=4.0, min_inliers=15, **match_args):
+    """Feed the verified geometry back into matching: match the descriptors of
+    every verified pair again, inside a band of ``threshold`` pixels around the
+    epipolar lines of its F (``sfm_io.match_descriptors_guided``).  It recovers
+    the matches that the unguided ratio test and cross-check lose to repeated
+    structure, and so lengthens the tracks.
+    ``verified`` is the tuple ``verify_pairs`` / ``verify_pairs_calibrated``
+    returned; the pairs with info >= 0 and n_inliers >= ``min_inliers`` are
+    taken, in ``verified``'s pair order, with their F from out[0].  In
+    ``MatchStore.pairs`` index1 is the observation in pair_ij[p, 0] and index2
+    the one in pair_ij[p, 1], and verify_pairs fits x2^T F x1 = 0 to
+    x1 = store[index1], x2 = store[index2]: for the pair (i, j) = pair_ij[p]
+    that is x_j^T F x_i = 0, the convention of the guided call, so F is passed
+    as it is and not transposed.  ``match_args`` (ratio, max_distance,
+    cross_check) go to ``match_descriptors_guided``, whose tuple (store,
+    pair_ij, match_start, a, b, dsq) is returned; its pair_ij holds the pairs
+    taken."""
+    _, pair_ij, out = verified[:3]
+    keep = (np.asarray(out[6]) >= 0) & (np.asarray(out[2]) >= min_inliers)
+    pairs = np.asarray(pair_ij, dtype=np.int64).reshape(-1, 2)[keep]
+    F = np.asarray(out[0], dtype=np.float64).reshape(-1, 3, 3)[keep]
+    return match_descriptors_guided(keypoints, descriptors, pairs, F, threshold=threshold, **match_args)
 
 
 def init_pairs(store, K, verified, Hh=128, seed=0, h_threshold=4.0, max_reproj=4.0, min_points=30, min_angle_deg=4.0,
