@@ -29,7 +29,8 @@ enum {
     SFM_ERR_HIP = -2,     /* HIP runtime error                           */
     SFM_ERR_NOMEM = -3,   /* device allocation failed                    */
     SFM_ERR_SOLVE = -4,   /* reduced camera system not positive definite */
-    SFM_ERR_COMM = -5     /* RCCL error                                  */
+    SFM_ERR_COMM = -5,    /* RCCL error                                  */
+    SFM_ERR_CAPACITY = -6 /* a result exceeds the caller's output arrays */
 };
 
 int sfm_version(void);
@@ -780,6 +781,98 @@ int sfm_match_descriptors_guided(const uint8_t *desc, const double *xy, int64_t 
                                  double gate, double ratio, int32_t max_dsq, int32_t cross_check, int64_t capacity,
                                  int64_t *match_start, int32_t *match_a, int32_t *match_b, int32_t *match_dsq,
                                  int32_t *nn, int32_t *d1, int32_t *d2, int32_t *nn_rev, int32_t *n_cand, int device);
+
+/* ---------------------------------------------------------------------
+ * Feature extraction: images to keypoints and descriptors, on the device.
+ * The stage in front of sfm_match_descriptors: a difference-of-Gaussians
+ * (DoG) detector after Lowe with the 128-byte gradient-histogram descriptor
+ * that sfm_match_descriptors takes.  The reference has no extractor.
+ * images is n_images x H x W uint8, row-major greyscale, all of one size.
+ * n_octaves == 0 means as many octaves as keep the smaller side >= 16.
+ * Definitions, from which every output follows; fp32 unless stated:
+ *   pixels are u8 / 255.  Octave 0 has the input's size (no up-sampling);
+ *     S = 3: an octave has S + 3 Gaussian layers and S + 2 DoG layers; layer
+ *     l carries sigma_l = sigma 2^(l/S).  The input is taken to carry blur
+ *     0.5: layer 0 of octave 0 is the input blurred by sqrt(sigma^2 - 0.25),
+ *     layer l > 0 is layer l - 1 blurred by sqrt(sigma_l^2 - sigma_(l-1)^2);
+ *     layer 0 of a later octave is every second pixel (0, 2, 4, ..) of layer
+ *     S of the octave before, so an octave of h x w is followed by one of
+ *     ceil(h/2) x ceil(w/2).
+ *   a blur of s is separable, rows then columns, radius R = ceil(4 s), the
+ *     2R + 1 taps exp(-i^2 / (2 s^2)) computed in fp64, normalised to sum 1,
+ *     then rounded to fp32; borders reflect-101; each output one fp32 sum.
+ *   D_l = G_(l+1) - G_l, one fp32 subtraction.
+ *   a candidate is a pixel (r, c) of D_l, 1 <= l <= S, 5 <= r < h - 5,
+ *     5 <= c < w - 5, with |D| > fp32(0.5 contrast_threshold / S) and D
+ *     strictly greater, or strictly smaller, than all 26 neighbours.
+ *   refinement: with the gradient g and the Hessian Hs of D by central
+ *     differences at (l, r, c), the offset X = (xc, xr, xs) solves Hs X = -g
+ *     (adjugate over determinant; rejected when the determinant is 0 or not
+ *     finite or a component reaches 1000).  While a component exceeds 0.5 in
+ *     magnitude the site moves by floor(X + 0.5), at most 5 times; rejected
+ *     when the sixth solve still exceeds 0.5, or the site leaves 1 <= l <= S
+ *     or the border of 5.  D^ = D + 0.5 g.X; rejected when |D^| S <
+ *     contrast_threshold, or when the 2 x 2 Hessian has det <= 0 or
+ *     tr^2 r >= (r + 1)^2 det with r = edge_threshold.
+ *     x = (c + xc) 2^octave, y = (r + xr) 2^octave (fp64 of the fp32 offsets;
+ *     pixel centres at integers of the input image), scale =
+ *     sigma 2^octave 2^((l + xs)/S), response = |D^|.
+ *   orientation: sigma_o = sigma 2^((l + xs)/S); over the pixels (r + i,
+ *     c + j), |i|, |j| <= floor(4.5 sigma_o + 0.5), strictly inside the layer
+ *     G_l, the gradient (G[y][x+1] - G[y][x-1], G[y+1][x] - G[y-1][x]) adds
+ *     its magnitude times exp(-(i^2 + j^2) / (2 (1.5 sigma_o)^2)) to bin
+ *     floor(36 atan2(dy, dx) / 2 pi + 0.5) mod 36 (angles in [0, 2 pi), from
+ *     +x towards +y).  The histogram is smoothed twice by the circular
+ *     [1 4 6 4 1] / 16.  Every bin above both neighbours and >= 0.8 of the
+ *     maximum gives a keypoint with angle (b + 0.5 (lo - hi) / (lo - 2 h +
+ *     hi)) 2 pi / 36 wrapped into [0, 2 pi), in radians.
+ *   descriptor: with (xo, yo) = (x, y) / 2^octave, hw = 3 scale / 2^octave,
+ *     every pixel of G_l strictly inside the layer and within
+ *     floor(hw 3.5355339 + 0.5) + 1 of (floor(xo + 0.5), floor(yo + 0.5)) is
+ *     rotated by -angle and divided by hw into (rx, ry); it contributes when
+ *     rx + 1.5 and ry + 1.5 lie in (-1, 4): its gradient magnitude times
+ *     exp(-(rx^2 + ry^2) / 8) is spread trilinearly over row ry + 1.5, column
+ *     rx + 1.5 and orientation bin 8 (atan2(gy, gx) - angle) / 2 pi mod 8;
+ *     entry ((row 4) + column) 8 + bin of 128.  L2-normalise, clamp at 0.2,
+ *     normalise again; byte = min(255, floor(512 v + 0.5)).
+ *   order: an image's keypoints are sorted by (octave, layer, row, column) of
+ *     the candidate they come from, then by orientation bin.  With
+ *     max_keypoints > 0 only the max_keypoints largest responses of an image
+ *     are kept, ties to the smaller key, emitted in key order.
+ * Outputs, caller-allocated, n_images x capacity rows each: image k owns rows
+ * [kp_start[k], kp_start[k+1]) (kp_start has n_images + 1 entries) of xy (fp64
+ * x, y), scale, angle, response (fp32) and desc (128 uint8).  An image with
+ * more than `capacity` keypoints (only possible with max_keypoints == 0) ends
+ * the call with SFM_ERR_CAPACITY and a message that names the image and its
+ * count; nothing is written out of bounds.  So does a cand_capacity below the
+ * candidates found.  Both are found while the chunks are processed: kp_start,
+ * the outputs and the diagnostics of the images of earlier chunks have been
+ * written by then and are valid, those of later images are not.
+ * Nullable diagnostics, never downloaded when null: kp_site (4 int32 per
+ * keypoint: octave, layer, row, col of the refined site); pyramid (per image
+ * the octaves, per octave the S + 3 layers, row-major fp32); and, together,
+ * cand_start (n_images + 1), cand (5 int32 per candidate: image, octave,
+ * layer, row, col, sorted), ref_ok, ref_site (3 int32: the final layer, row,
+ * col) and ref_val (4 fp32: xc, xr, xs, |D^|) per candidate, zero where
+ * rejected; cand_capacity is the rows they hold in total.
+ * SFM_ERR_ARG, found on the host before a device is looked for, with nothing
+ * written: a null required pointer; H or W below 16 or above 65536 (the
+ * candidate key's 17 bits); n_octaves < 0 or above the maximum for the size; a
+ * threshold or sigma that is not finite or not positive; sigma <= 0.5 (the
+ * input's assumed blur) or above 3.2 (a blur radius above 25, the tile the
+ * blur kernel's LDS is laid out for: a limit of this implementation, not of
+ * the algorithm); max_keypoints < 0; capacity below max_keypoints.
+ * n_images == 0 succeeds without a device.
+ * The images are processed in chunks; the workspace does not grow with
+ * n_images.  Every output is the same from run to run.
+ * sfm_last_timings: upload, kernels, download, the pyramid kernels (blurs
+ * and down-samples) alone; each summed over the chunks.
+ * ------------------------------------------------------------------- */
+int sfm_extract_features(const uint8_t *images, int32_t n_images, int32_t H, int32_t W, int32_t n_octaves,
+                         int32_t max_keypoints, double contrast_threshold, double edge_threshold, double sigma,
+                         int64_t capacity, int64_t *kp_start, double *xy, float *scale, float *angle, float *response,
+                         uint8_t *desc, int32_t *kp_site, float *pyramid, int64_t cand_capacity, int64_t *cand_start,
+                         int32_t *cand, uint8_t *ref_ok, int32_t *ref_site, float *ref_val, int device);
 
 /* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)

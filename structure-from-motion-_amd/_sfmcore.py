@@ -33,6 +33,7 @@ _u32 = ctypes.POINTER(ctypes.c_uint32)
 _i64 = ctypes.POINTER(ctypes.c_int64)
 _u8 = ctypes.POINTER(ctypes.c_uint8)
 _u64 = ctypes.POINTER(ctypes.c_uint64)
+_f32 = ctypes.POINTER(ctypes.c_float)
 _c = ctypes.c_int
 _i = ctypes.c_int64
 _v = ctypes.c_void_p
@@ -122,6 +123,9 @@ SIGNATURES = [
     ("sfm_match_descriptors_guided", _c, [_u8, _d, _i, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _d, _i,
                                           ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _i, _i64,
                                           _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c]),
+    ("sfm_extract_features", _c, [_u8, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _i64, _d, _f32, _f32, _f32,
+                                  _u8, _i32, _f32, _i, _i64, _i32, _u8, _i32, _f32, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -1246,6 +1250,84 @@ def match_descriptors_guided(desc, xy, img_start, pairs, F, gate, ratio=0.8, max
                                              _p(outs[0], _i64), *(_p(o, _i32) for o in outs[1:]),
                                              *(None if d is None else _p(d, _i32) for d in diag), DEVICE))
     return _match_result(outs, diag, ("nn", "d1", "d2", "nn_rev", "n_cand"), want_diagnostics)
+
+
+EXTRACT_DEFAULT_CAPACITY = 32768
+
+
+def extract_octaves(H, W):
+    """the octaves that keep the smaller side of an H x W image >= 16, each taking every second pixel"""
+    n = 0
+    while min(H, W) >= 16:
+        n, H, W = n + 1, (H + 1) // 2, (W + 1) // 2
+    return n
+
+
+def extract_features(images, n_octaves=0, max_keypoints=0, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6,
+                     capacity=None, want_diagnostics=False, cand_capacity=None):
+    """Feature extraction (sfm_extract_features): difference-of-Gaussians
+    keypoints with 128-byte gradient-histogram descriptors of ``images``
+    (n, H, W) uint8, on the device; include/sfmcore.h has the definitions.
+    n_octaves 0 means as many as keep the smaller side >= 16.  ``capacity`` is
+    the rows per image of the outputs, which are allocated here as n x
+    capacity rows of 172 bytes (default: max_keypoints, or without a cap
+    EXTRACT_DEFAULT_CAPACITY = 32768 or the bound on an image's candidates if
+    that is smaller; an image with more keypoints ends the call with an
+    SfmCoreError that names the image and its count).  Returns a dict: kp_start (n + 1,) int64 -- image k owns
+    rows kp_start[k]:kp_start[k + 1] -- xy (N, 2) fp64, scale, angle, response
+    (N,) fp32, desc (N, 128) uint8; with want_diagnostics also kp_site (N, 4)
+    int32 (octave, layer, row, col), pyramid (n, floats per image) fp32,
+    cand_start (n + 1,), cand (C, 5) int32 (image, octave, layer, row, col),
+    ref_ok (C,) bool, ref_site (C, 3) int32 and ref_val (C, 4) fp32 (xc, xr,
+    xs, |D^|).  The arguments are checked before a device is looked for;
+    no images need no device."""
+    images = np.ascontiguousarray(images, dtype=np.uint8)
+    if images.ndim != 3:
+        raise ValueError("extract_features: images must be (n, H, W)")
+    n, H, W = images.shape
+    n_oct = int(n_octaves) if n_octaves else extract_octaves(H, W)
+    per_image = bound = 0
+    h, w = H, W
+    for _ in range(max(min(n_oct, 16), 0)):
+        per_image += 6 * h * w
+        bound += 6 * ((h + 1) // 2) * ((w + 1) // 2)
+        h, w = (h + 1) // 2, (w + 1) // 2
+    if capacity is None:
+        capacity = int(max_keypoints) if max_keypoints > 0 else min(bound, EXTRACT_DEFAULT_CAPACITY)
+    capacity = int(capacity)
+    rows = n * max(capacity, 0)
+    kp_start = np.zeros(n + 1, dtype=np.int64)
+    xy = np.zeros((rows, 2), dtype=np.float64)
+    scale, angle, response = (np.zeros(rows, dtype=np.float32) for _ in range(3))
+    desc = np.zeros((rows, 128), dtype=np.uint8)
+    site = pyramid = cand_start = cand = ref_ok = ref_site = ref_val = None
+    cc = 0
+    if want_diagnostics:
+        cc = n * bound if cand_capacity is None else int(cand_capacity)
+        site = np.zeros((rows, 4), dtype=np.int32)
+        pyramid = np.zeros((n, per_image), dtype=np.float32)
+        cand_start = np.zeros(n + 1, dtype=np.int64)
+        cand = np.zeros((cc, 5), dtype=np.int32)
+        ref_ok = np.zeros(cc, dtype=np.uint8)
+        ref_site = np.zeros((cc, 3), dtype=np.int32)
+        ref_val = np.zeros((cc, 4), dtype=np.float32)
+
+    def ptr(a, t):
+        return None if a is None else _p(a, t)
+    _check(_lib.sfm_extract_features(_p(images, _u8), n, H, W, int(n_octaves), int(max_keypoints),
+                                     float(contrast_threshold), float(edge_threshold), float(sigma), capacity,
+                                     _p(kp_start, _i64), _p(xy), _p(scale, _f32), _p(angle, _f32), _p(response, _f32),
+                                     _p(desc, _u8), ptr(site, _i32), ptr(pyramid, _f32), cc, ptr(cand_start, _i64),
+                                     ptr(cand, _i32), ptr(ref_ok, _u8), ptr(ref_site, _i32), ptr(ref_val, _f32),
+                                     DEVICE))
+    N = int(kp_start[-1])
+    out = dict(kp_start=kp_start, xy=xy[:N].copy(), scale=scale[:N].copy(), angle=angle[:N].copy(),
+               response=response[:N].copy(), desc=desc[:N].copy())
+    if want_diagnostics:
+        C = int(cand_start[-1])
+        out.update(kp_site=site[:N].copy(), pyramid=pyramid, cand_start=cand_start, cand=cand[:C].copy(),
+                   ref_ok=ref_ok[:C].astype(bool), ref_site=ref_site[:C].copy(), ref_val=ref_val[:C].copy())
+    return out
 
 
 def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,

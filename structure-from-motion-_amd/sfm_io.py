@@ -305,6 +305,68 @@ def match_descriptors_guided(keypoints, descriptors, pairs, F, threshold=4.0, ra
     return store, pair_ij, out["match_start"], out["a"], out["b"], out["dsq"]
 
 
+def extract_features(images, n_octaves=None, max_keypoints=0, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6,
+                     capacity=None):
+    """Keypoints and descriptors of greyscale images, on the device
+    (sfm_extract_features): the first stage, in front of match_descriptors, for
+    images that come without features.  ``images`` is a list or array of 2-D
+    uint8 images, all H x W (a caller groups images by size); H, W >= 16.  A
+    difference-of-Gaussians detector after Lowe -- octave 0 at the input's size,
+    3 layers per octave, ``n_octaves`` octaves (None: as many as keep the
+    smaller side >= 16), extrema of |D| above ``contrast_threshold`` refined by
+    a quadratic fit and tested against ``edge_threshold`` -- with one keypoint
+    per dominant gradient orientation and the 128-byte gradient-histogram
+    descriptor that the matcher takes (include/sfmcore.h has every
+    definition).  ``sigma`` is the blur of an octave's first layer, in
+    (0.5, 3.2].  With ``max_keypoints`` > 0 an image keeps its that many
+    largest responses.  The host arrays of a call hold ``capacity`` keypoints
+    per image, 172 bytes each: by default max_keypoints, or without a cap
+    32,768 (200 images: 1.1 GB); an image with more keypoints raises
+    SfmCoreError with its count, and the caller passes a larger ``capacity``
+    or a cap.
+    Returns (keypoints, descriptors, scale, angle, response), each a list with
+    one entry per image: keypoints[k] (N_k, 2) fp64 x, y with pixel centres at
+    integers, as in the MatchStore; descriptors[k] (N_k, 128) uint8; scale[k],
+    angle[k] (radians in [0, 2 pi), from +x towards +y) and response[k] (N_k,)
+    fp32.  An image's keypoints are ordered by (octave, layer, row, column,
+    orientation bin) and are the same from run to run.  keypoints and
+    descriptors go unchanged into match_descriptors, match_descriptors_guided
+    and rematch_verified."""
+    name = "extract_features"
+    imgs = [np.asarray(im) for im in images]
+    for im in imgs:
+        if im.dtype != np.uint8 or im.ndim != 2:
+            raise ValueError(f"{name}: images[k] must be a 2-D uint8 array")
+        if im.shape != imgs[0].shape:
+            raise ValueError(f"{name}: the images differ in size; group them by size")
+    if n_octaves is not None and (int(n_octaves) != n_octaves or n_octaves < 1):
+        raise ValueError(f"{name}: n_octaves must be None or a positive integer")
+    if int(max_keypoints) != max_keypoints or max_keypoints < 0:
+        raise ValueError(f"{name}: max_keypoints must be an integer >= 0")
+    for label, v in (("contrast_threshold", contrast_threshold), ("edge_threshold", edge_threshold)):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name}: {label} must be finite and > 0")
+    if capacity is not None and (int(capacity) != capacity or capacity < max(int(max_keypoints), 1)):
+        raise ValueError(f"{name}: capacity must be a positive integer, at least max_keypoints")
+    if not (np.isfinite(sigma) and 0.5 < sigma <= 3.2):
+        raise ValueError(f"{name}: sigma must be in (0.5, 3.2]")
+    if not imgs:
+        return [], [], [], [], []
+    H, W = imgs[0].shape
+    if H < 16 or W < 16:
+        raise ValueError(f"{name}: the images must be at least 16 x 16")
+    if n_octaves is not None and n_octaves > _core.extract_octaves(H, W):
+        raise ValueError(f"{name}: n_octaves above the {_core.extract_octaves(H, W)} octaves that keep the smaller "
+                         "side >= 16")
+    out = _core.extract_features(np.stack(imgs), 0 if n_octaves is None else int(n_octaves), int(max_keypoints),
+                                 float(contrast_threshold), float(edge_threshold), float(sigma),
+                                 capacity=None if capacity is None else int(capacity))
+    st = out["kp_start"]
+    per_image = [[out[k][st[i]:st[i + 1]].copy() for i in range(len(imgs))]
+                 for k in ("xy", "desc", "scale", "angle", "response")]
+    return tuple(per_image)
+
+
 def _match_inputs(name, keypoints, descriptors, pairs, ratio, max_distance):
     """The input checks that the matching calls share.  Returns (keypoints as
     fp64 arrays, desc, img_start, pair_ij, max_dsq)."""
