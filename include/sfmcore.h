@@ -875,6 +875,80 @@ int sfm_extract_features(const uint8_t *images, int32_t n_images, int32_t H, int
                          int32_t *cand, uint8_t *ref_ok, int32_t *ref_site, float *ref_val, int device);
 
 /* ---------------------------------------------------------------------
+ * Visual vocabulary: k-means on uint8 descriptors with uint8 centres, on the
+ * device; with max_iterations == 0 the quantisation of descriptors against a
+ * given vocabulary.  With sfm_select_pairs the stage that chooses the image
+ * pairs sfm_match_descriptors is given; the reference has no such stage.
+ * desc is n x dim uint8, row-major, dim 64, 128 or 256; centres is
+ * n_words x dim uint8, on entry the initial centres, on return the final ones.
+ * Definitions, from which every output follows; everything is integer:
+ *   dsq: sfm_match_descriptors' squared distance, exact in int32;
+ *   word_t[a]: the first centre of the (dsq, centre index) order over
+ *     centres_t;
+ *   cnt_t[w]: the number of members of centre w (the a with word_t[a] == w);
+ *   sum_t[w][k]: the exact integer sum of byte k over the members of w;
+ *   centres_(t+1)[w][k] = floor((2 sum_t[w][k] + cnt_t[w]) / (2 cnt_t[w]))
+ *     when cnt_t[w] > 0 -- the mean rounded half up -- and centres_t[w][k]
+ *     otherwise: an empty cluster keeps its centre;
+ *   inertia[t] = the sum over a of dsq(a, centres_t[word_t[a]]), as int64;
+ *   updates run for t = 1, 2, ...: the loop stops after update T when
+ *     T == max_iterations or when update T changed no byte; *iterations = T.
+ * Outputs, caller-allocated: centres_T, word_T (n, nullable), cnt_T (count,
+ * n_words, nullable), inertia[0 .. T] (max_iterations + 1 entries, nullable;
+ * entries past T are not written) and *iterations.
+ * SFM_ERR_ARG, found on the host before a device is looked for, with nothing
+ * written: a null required pointer; dim not 64, 128 or 256; n < 1; n_words
+ * < 1, above n or above 2^20; max_iterations < 0; and n above 2^24 with
+ * max_iterations > 0 -- the byte sums are 32-bit (255 * 2^24 < 2^32), a limit
+ * of this implementation; quantisation (max_iterations == 0) has no such
+ * limit.
+ * Every output is the same from run to run (integer minima and integer
+ * atomics, which are order-independent).
+ * sfm_last_timings: upload, kernels, download.
+ * ------------------------------------------------------------------- */
+int sfm_vocab_train(const uint8_t *desc, int64_t n, int32_t dim, int32_t n_words, int32_t max_iterations,
+                    uint8_t *centres, int32_t *word, int64_t *count, int64_t *inertia, int32_t *iterations,
+                    int device);
+
+/* ---------------------------------------------------------------------
+ * Pair selection: tf-idf retrieval over quantised words, the top_k
+ * neighbours of every image.  word is n_kp int32 in [0, n_words) (what
+ * sfm_vocab_train returns); image k owns the keypoints
+ * [img_start[k], img_start[k+1]) (n_images + 1 entries).
+ * Definitions, from which every output follows; integer work except the
+ * score:
+ *   h[i][w]: the number of keypoints of image i with word w;
+ *   df[w]: the number of images with h[i][w] > 0;
+ *   q[d] = floor(256 log((double)n_images / (double)d) + 0.5) for
+ *     1 <= d <= n_images, a table the host computes with the C library's log
+ *     (the device never calls log); a word in every image weighs 0;
+ *   v[i][w] = h[i][w] q[df[w]];
+ *   norm2[i] = the sum over w of v[i][w]^2 and dot(i, j) = the sum over w of
+ *     v[i][w] v[j][w], both exact in int64;
+ *   score(i, j) = (double)dot / (sqrt((double)norm2[i]) sqrt((double)norm2[j])):
+ *     five IEEE fp64 operations in this order;
+ *   the candidates of i are the j != i with dot(i, j) > 0, ordered by score
+ *     descending and then by j ascending.
+ * Outputs, caller-allocated: row i of neighbour, score and dot (nullable)
+ * (n_images x top_k each) holds the first top_k candidates of i, padded with
+ * -1, 0.0 and 0; norm2 (n_images) and df (n_words) are nullable.
+ * SFM_ERR_ARG, found on the host before a device is looked for, with nothing
+ * written: a null required pointer; img_start not starting at 0, decreasing
+ * or not ending at n_kp; a word outside [0, n_words); an image with more than
+ * 2^18 keypoints; n_images above 16,384; n_words outside [1, 2^20];
+ * top_k < 0.  The two limits are limits of this implementation: they keep dot
+ * inside int64 (q < 2^12, so q^2 N_i N_j < 2^24 2^36) and let a query's row of
+ * int64 accumulators fit in the 160 KB of LDS (16,384 x 8 B = 128 KB).
+ * n_images == 0 or top_k == 0 succeeds without a device, with nothing
+ * written; so does n_kp == 0, with every row padding, norm2 and df zero.
+ * Every output is the same from run to run.
+ * sfm_last_timings: upload, kernels, download.
+ * ------------------------------------------------------------------- */
+int sfm_select_pairs(const int32_t *word, int64_t n_kp, const int64_t *img_start, int32_t n_images,
+                     int32_t n_words, int32_t top_k, int32_t *neighbour, double *score, int64_t *dot,
+                     int64_t *norm2, int32_t *df, int device);
+
+/* ---------------------------------------------------------------------
  * BundleAdjustment (BundleAdjustment.py:8-242)
  * Camera parameters are the reference's: [rotvec(3), t(3)] with
  * x_cam = R(rotvec) X + t, proj = K x_cam [:2] / (K x_cam [2] + 1e-8),

@@ -126,6 +126,9 @@ SIGNATURES = [
     ("sfm_extract_features", _c, [_u8, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _i64, _d, _f32, _f32, _f32,
                                   _u8, _i32, _f32, _i, _i64, _i32, _u8, _i32, _f32, _c]),
+    ("sfm_vocab_train", _c, [_u8, _i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _u8, _i32, _i64, _i64, _i32, _c]),
+    ("sfm_select_pairs", _c, [_i32, _i, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32, _d, _i64, _i64,
+                              _i32, _c]),
     ("sfm_project_points", _c, [_d, _d, _i, _d, _c]),
     ("sfm_reduced_solve", _c, [_d, _d, ctypes.c_int32, _d, _c]),
     ("sfm_ba_residuals", _c, [ctypes.c_int32, _i, _i, _i32, _i32, _d, _d, _d, _d, _d, _c]),
@@ -1328,6 +1331,58 @@ def extract_features(images, n_octaves=0, max_keypoints=0, contrast_threshold=0.
         out.update(kp_site=site[:N].copy(), pyramid=pyramid, cand_start=cand_start, cand=cand[:C].copy(),
                    ref_ok=ref_ok[:C].astype(bool), ref_site=ref_site[:C].copy(), ref_val=ref_val[:C].copy())
     return out
+
+
+def vocab_train(desc, centres, max_iterations=10):
+    """Visual vocabulary (sfm_vocab_train): k-means on the uint8 descriptors
+    desc (n, dim), dim 64, 128 or 256, from the initial ``centres``
+    (n_words, dim) uint8, on the device; max_iterations = 0 is the quantisation
+    of desc against centres.  Exact integer work (include/sfmcore.h): a
+    descriptor goes to the first centre of the (dsq, index) order, a centre
+    becomes the mean of its members rounded half up, an empty cluster keeps its
+    centre, and the loop stops after update T when T == max_iterations or
+    nothing changed.  Returns a dict: centres (n_words, dim) uint8, word (n,)
+    int32, count (n_words,) int64, inertia (T + 1,) int64 and iterations = T.
+    The arguments are checked before a device is looked for."""
+    desc = np.ascontiguousarray(desc, dtype=np.uint8)
+    centres = np.array(centres, dtype=np.uint8, order="C")  # a copy: the call writes it
+    if desc.ndim != 2 or centres.ndim != 2 or centres.shape[1] != desc.shape[1]:
+        raise ValueError("vocab_train: desc must be (n, dim) and centres (n_words, dim)")
+    n, n_words, its = len(desc), len(centres), int(max_iterations)
+    word = np.full(n, -1, dtype=np.int32)
+    count = np.zeros(n_words, dtype=np.int64)
+    inertia = np.zeros(max(its, 0) + 1, dtype=np.int64)
+    T = np.zeros(1, dtype=np.int32)
+    _check(_lib.sfm_vocab_train(_p(desc, _u8), n, desc.shape[1], n_words, its, _p(centres, _u8), _p(word, _i32),
+                                _p(count, _i64), _p(inertia, _i64), _p(T, _i32), DEVICE))
+    return dict(centres=centres, word=word, count=count, inertia=inertia[:int(T[0]) + 1].copy(), iterations=int(T[0]))
+
+
+def select_pairs(word, img_start, n_words, top_k=20):
+    """Pair selection (sfm_select_pairs): tf-idf retrieval over the words
+    (n_kp,) int32 in [0, n_words) of the images' keypoints -- image k owns
+    img_start[k]:img_start[k + 1] -- on the device.  With h the word counts of
+    an image, df the images per word and q[d] = floor(256 log(n_images / d) +
+    0.5), v = h q[df]; norm2 and dot are exact int64, score = dot /
+    (sqrt(norm2_i) sqrt(norm2_j)), and the neighbours of i are the j != i with
+    dot > 0 by (score descending, j ascending).  Returns a dict: neighbour
+    (n_images, top_k) int32 padded with -1, score (n_images, top_k) fp64 padded
+    with 0, dot (n_images, top_k) int64 padded with 0, norm2 (n_images,) int64
+    and df (n_words,) int32.  The arguments are checked before a device is
+    looked for; no images, or top_k == 0, need no device."""
+    word = np.ascontiguousarray(word, dtype=np.int32).reshape(-1)
+    st = np.ascontiguousarray(img_start, dtype=np.int64).reshape(-1)
+    if len(st) < 1:
+        raise ValueError("select_pairs: img_start needs n_images + 1 entries")
+    n_images, k = len(st) - 1, int(top_k)
+    neighbour = np.full((n_images, max(k, 0)), -1, dtype=np.int32)
+    score = np.zeros((n_images, max(k, 0)), dtype=np.float64)
+    dot = np.zeros((n_images, max(k, 0)), dtype=np.int64)
+    norm2 = np.zeros(n_images, dtype=np.int64)
+    df = np.zeros(max(int(n_words), 0), dtype=np.int32)
+    _check(_lib.sfm_select_pairs(_p(word, _i32), len(word), _p(st, _i64), n_images, int(n_words), k,
+                                 _p(neighbour, _i32), _p(score), _p(dot, _i64), _p(norm2, _i64), _p(df, _i32), DEVICE))
+    return dict(neighbour=neighbour, score=score, dot=dot, norm2=norm2, df=df)
 
 
 def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,

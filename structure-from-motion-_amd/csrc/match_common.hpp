@@ -64,6 +64,149 @@ __device__ __forceinline__ void md_merge(int32_t &m1, int32_t &i1, int32_t &m2, 
     i1 = other ? oi1 : i1;
 }
 
+// The nearest-neighbour pass that match_descriptors.hip describes (k_md_nn
+// there): sfm_match_descriptors instantiates it for image pairs, and
+// retrieval.hip for blocks of descriptors against a vocabulary's centres.
+// pairs is (first, second) per pair when !SWAP and read as (second, first) when
+// SWAP; row_off[p] is where the pair's rows start in nn / d1 / d2.
+template <int DIM, bool SWAP>
+__global__ __launch_bounds__(MD_THREADS) void k_md_nn(const uint8_t *__restrict__ desc, const int32_t *__restrict__ norm,
+                                                      const int64_t *__restrict__ img_start,
+                                                      const int32_t *__restrict__ pairs, int64_t P,
+                                                      const int64_t *__restrict__ row_off, int32_t *__restrict__ nn,
+                                                      int32_t *__restrict__ d1, int32_t *__restrict__ d2) {
+    constexpr int KS = DIM / 64;                          // k steps
+    constexpr int STRIDE = DIM + MD_PAD;                  // bytes of an LDS row
+    constexpr int CH = DIM / 16;                          // 16-byte chunks per row
+    constexpr int NQ = MD_TN * CH / MD_THREADS;           // chunks a thread stages per tile
+    static_assert(MD_TN * CH % MD_THREADS == 0, "a tile is a whole number of passes");
+    __shared__ __attribute__((aligned(16))) uint8_t sB[2][MD_TN * STRIDE];
+    __shared__ int32_t sNb[2][MD_TN];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    for (int64_t p = blockIdx.y; p < P; p += gridDim.y) {
+        const int32_t ii = pairs[2 * p + (SWAP ? 1 : 0)], jj = pairs[2 * p + (SWAP ? 0 : 1)];
+        const int64_t is = img_start[ii], js = img_start[jj];
+        const int32_t ni = (int32_t)(img_start[ii + 1] - is), nj = (int32_t)(img_start[jj + 1] - js);
+        const int32_t row0 = (int32_t)blockIdx.x * MD_BM;
+        if (row0 >= ni) continue;  // uniform over the workgroup
+        const int32_t wrow0 = row0 + wave * (MD_MS * 16);
+
+        // this wave's rows, biased, in registers
+        md_v4i a[MD_MS][KS];
+#pragma unroll
+        for (int ms = 0; ms < MD_MS; ++ms) {
+            const int32_t r = wrow0 + ms * 16 + lr;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                md_v4i v = {0, 0, 0, 0};
+                if (r < ni) {
+                    v = *reinterpret_cast<const md_v4i *>(desc + (is + r) * DIM + ks * 64 + lk * 16);
+                    v ^= (int)0x80808080;
+                }
+                a[ms][ks] = v;
+            }
+        }
+        int32_t m1[MD_MS][4], i1[MD_MS][4], m2[MD_MS][4];
+#pragma unroll
+        for (int ms = 0; ms < MD_MS; ++ms)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                m1[ms][j] = MD_NONE;
+                m2[ms][j] = MD_NONE;
+                i1[ms][j] = -1;
+            }
+
+        const int32_t ntiles = (nj + MD_TN - 1) / MD_TN;
+        md_v4i st[NQ];
+        int32_t st_nb = MD_OUTSIDE;
+        // tile t of the second image: global -> registers, registers -> LDS buffer
+        auto fetch = [&](int32_t t) {
+            const int32_t c0 = t * MD_TN;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int c = tid + q * MD_THREADS, col = c / CH, kc = c % CH;
+                md_v4i v = {0, 0, 0, 0};
+                if (c0 + col < nj) {
+                    v = *reinterpret_cast<const md_v4i *>(desc + (js + c0 + col) * DIM + kc * 16);
+                    v ^= (int)0x80808080;
+                }
+                st[q] = v;
+            }
+            if (tid < MD_TN) st_nb = c0 + tid < nj ? norm[js + c0 + tid] : MD_OUTSIDE;
+        };
+        auto stash = [&](int buf) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int c = tid + q * MD_THREADS, col = c / CH, kc = c % CH;
+                *reinterpret_cast<md_v4i *>(&sB[buf][col * STRIDE + kc * 16]) = st[q];
+            }
+            if (tid < MD_TN) sNb[buf][tid] = st_nb;
+        };
+
+        __syncthreads();  // the previous pair's last tile is no longer read
+        if (ntiles > 0) {
+            fetch(0);
+            stash(0);
+        }
+        __syncthreads();
+        for (int32_t t = 0; t < ntiles; ++t) {
+            const int cur = t & 1;
+            if (t + 1 < ntiles) fetch(t + 1);
+#pragma unroll
+            for (int ns = 0; ns < MD_TN / 16; ++ns) {
+                md_v4i b[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    b[ks] = *reinterpret_cast<const md_v4i *>(&sB[cur][(ns * 16 + lr) * STRIDE + ks * 64 + lk * 16]);
+                const int32_t nb = sNb[cur][ns * 16 + lr];
+                const int32_t col = t * MD_TN + ns * 16 + lr;
+#pragma unroll
+                for (int ms = 0; ms < MD_MS; ++ms) {
+                    md_v4i acc = {0, 0, 0, 0};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks)
+                        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[ms][ks], b[ks], acc, 0, 0, 0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int32_t w = nb - 2 * acc[j];
+                        const int32_t lo = m1[ms][j];
+                        // the second smallest so far: the median of (m1 <= m2, w)
+                        m2[ms][j] = min(m2[ms][j], max(lo, w));
+                        i1[ms][j] = w < lo ? col : i1[ms][j];
+                        m1[ms][j] = min(lo, w);
+                    }
+                }
+            }
+            if (t + 1 < ntiles) stash(cur ^ 1);
+            __syncthreads();
+        }
+
+        // the 16 lanes that share a row (the same lane >> 4), then the row's outputs
+#pragma unroll
+        for (int ms = 0; ms < MD_MS; ++ms)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int32_t x1 = m1[ms][j], xi = i1[ms][j], x2 = m2[ms][j];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) {
+                    const int32_t o1 = __shfl_xor(x1, o), oi = __shfl_xor(xi, o), o2 = __shfl_xor(x2, o);
+                    md_merge(x1, xi, x2, o1, oi, o2);
+                }
+                const int32_t r = wrow0 + ms * 16 + lk * 4 + j;
+                if (lr == 0 && r < ni) {
+                    const int32_t na = norm[is + r];
+                    const bool has1 = x1 < MD_VALID, has2 = x2 < MD_VALID;
+                    const int64_t o = row_off[p] + r;
+                    nn[o] = has1 ? xi : -1;
+                    if (d1) d1[o] = has1 ? na + x1 : MD_NONE;
+                    if (d2) d2[o] = has2 ? na + x2 : MD_NONE;
+                }
+            }
+    }
+}
+
 // flag[row_off[p] + a] = 1 when keypoint a of the pair's first image is matched
 static __global__ __launch_bounds__(MD_THREADS) void k_md_accept(const int64_t *img_start, const int32_t *pairs,
                                                                  int64_t P, const int64_t *row_off,

@@ -367,6 +367,120 @@ def extract_features(images, n_octaves=None, max_keypoints=0, contrast_threshold
     return tuple(per_image)
 
 
+def _retrieval_inputs(name, descriptors):
+    """The input checks that the retrieval calls share.  Returns (desc,
+    img_start) of the per-image descriptor arrays."""
+    descs = [np.asarray(d) for d in descriptors]
+    for d in descs:
+        if d.dtype != np.uint8 or d.ndim != 2:
+            raise ValueError(f"{name}: descriptors[k] must be (N_k, dim) uint8")
+        if d.shape[1] != descs[0].shape[1]:
+            raise ValueError(f"{name}: the descriptors differ in length")
+    if not descs or sum(len(d) for d in descs) == 0:
+        raise ValueError(f"{name}: no descriptors")
+    if descs[0].shape[1] not in (64, 128, 256):
+        raise ValueError(f"{name}: the descriptor length must be 64, 128 or 256")
+    desc = np.ascontiguousarray(np.concatenate(descs))
+    img_start = np.concatenate([[0], np.cumsum([len(d) for d in descs])]).astype(np.int64)
+    return desc, img_start
+
+
+def _centres_of(name, centres, dim):
+    centres = np.asarray(centres)
+    if centres.dtype != np.uint8 or centres.ndim != 2 or centres.shape[1] != dim or len(centres) < 1:
+        raise ValueError(f"{name}: centres must be (n_words, dim) uint8 with the descriptors' dim")
+    return centres
+
+
+def train_vocabulary(descriptors, n_words, iterations=10, seed=0, max_rows=None):
+    """A visual vocabulary of the images' descriptors, on the device
+    (sfm_vocab_train): k-means with exact integer arithmetic on
+    ``descriptors[k]`` (N_k, dim) uint8, dim 64, 128 or 256.  With ``max_rows``
+    below the descriptor count, training uses the deterministic subsample of
+    rows floor(k n / max_rows), k = 0 .. max_rows - 1, of the concatenated
+    descriptors.  The initial centres are the rows
+    np.sort(np.random.default_rng(seed).choice(n, n_words, replace=False)) of
+    the training rows; ``n_words`` is clipped to their number.  A descriptor
+    belongs to its nearest centre (ties to the smaller index), a centre becomes
+    its members' mean rounded half up, an empty cluster keeps its centre, and
+    the loop stops after ``iterations`` updates or when nothing changed.
+    Returns (centres, report): centres (n_words, dim) uint8 and report a dict
+    with word (the training rows' words), count, inertia (one entry per
+    assignment, T + 1) and iterations = T.  The result is the same from run to
+    run."""
+    name = "train_vocabulary"
+    desc, _ = _retrieval_inputs(name, descriptors)
+    if int(n_words) != n_words or n_words < 1:
+        raise ValueError(f"{name}: n_words must be a positive integer")
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError(f"{name}: iterations must be an integer >= 0")
+    if max_rows is not None:
+        if int(max_rows) != max_rows or max_rows < 1:
+            raise ValueError(f"{name}: max_rows must be None or a positive integer")
+        if max_rows < len(desc):
+            desc = np.ascontiguousarray(desc[(np.arange(int(max_rows), dtype=np.int64) * len(desc)) // int(max_rows)])
+    n = len(desc)
+    n_words = min(int(n_words), n)
+    first = np.sort(np.random.default_rng(seed).choice(n, n_words, replace=False))
+    out = _core.vocab_train(desc, desc[first], int(iterations))
+    return out.pop("centres"), out
+
+
+def quantize(descriptors, centres):
+    """The words of the images' descriptors in a vocabulary, on the device
+    (sfm_vocab_train without an update): for every row of ``descriptors[k]``
+    the nearest of ``centres`` (n_words, dim) uint8 by exact integer squared
+    distance, ties to the smaller index.  Returns a list with one (N_k,) int32
+    array per image."""
+    desc, img_start = _retrieval_inputs("quantize", descriptors)
+    centres = _centres_of("quantize", centres, desc.shape[1])
+    if len(centres) > len(desc):
+        raise ValueError("quantize: more centres than descriptors")
+    word = _core.vocab_train(desc, centres, 0)["word"]
+    return [word[img_start[k]:img_start[k + 1]].copy() for k in range(len(img_start) - 1)]
+
+
+def neighbour_pairs(neighbour):
+    """The unique (min(i, j), max(i, j)) over the non-negative entries j of row
+    i of ``neighbour``, sorted lexicographically: (P, 2) int32."""
+    neighbour = np.asarray(neighbour)
+    if neighbour.ndim != 2:
+        raise ValueError("neighbour_pairs: neighbour must be (n_images, top_k)")
+    i, k = np.nonzero(neighbour >= 0)
+    j = neighbour[i, k]
+    ij = np.stack([np.minimum(i, j), np.maximum(i, j)], axis=1).reshape(-1, 2)
+    return np.unique(ij, axis=0).astype(np.int32).reshape(-1, 2)
+
+
+def select_pairs(descriptors, centres=None, n_words=4096, top_k=20, iterations=10, seed=0):
+    """Choose the image pairs to match by image retrieval, on the device: the
+    stage between extract_features and match_descriptors for collections whose
+    order says nothing.  The descriptors are quantised against ``centres``
+    (default: a vocabulary of ``n_words`` words trained on them by
+    train_vocabulary with ``iterations`` and ``seed``; n_words is clipped to the
+    number of descriptors), every image becomes a tf-idf vector over the words
+    and gets its ``top_k`` most similar images (sfm_select_pairs: integer
+    weights floor(256 log(n_images / df) + 0.5), exact int64 dot products, the
+    cosine as the score, ties to the smaller image number; an image with fewer
+    candidates has its row padded with -1).
+    Returns (pairs, neighbour, score, centres): pairs (P, 2) int32, the unique
+    (min(i, j), max(i, j)) over all neighbours, sorted -- exactly what
+    match_descriptors(pairs=...) takes -- neighbour (n_images, top_k) int32,
+    score (n_images, top_k) fp64 and the vocabulary used."""
+    name = "select_pairs"
+    desc, img_start = _retrieval_inputs(name, descriptors)
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"{name}: top_k must be an integer >= 0")
+    if centres is None:
+        centres, _ = train_vocabulary(descriptors, n_words, iterations, seed)
+    centres = _centres_of(name, centres, desc.shape[1])
+    if len(centres) > len(desc):
+        raise ValueError(f"{name}: more centres than descriptors")
+    word = _core.vocab_train(desc, centres, 0)["word"]
+    out = _core.select_pairs(word, img_start, len(centres), int(top_k))
+    return neighbour_pairs(out["neighbour"]), out["neighbour"], out["score"], centres
+
+
 def _match_inputs(name, keypoints, descriptors, pairs, ratio, max_distance):
     """The input checks that the matching calls share.  Returns (keypoints as
     fp64 arrays, desc, img_start, pair_ij, max_dsq)."""

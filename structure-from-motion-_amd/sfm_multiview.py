@@ -29,6 +29,7 @@ import numpy as np
 import _sfmcore as _core
 from sfm_io import merge_tracks  # noqa: F401  (the stage list's first entry lives with the store)
 from sfm_io import extract_features  # noqa: F401  (the first stage: images to keypoints and descriptors)
+from sfm_io import train_vocabulary, quantize, select_pairs  # noqa: F401  (which pairs to match: retrieval)
 from sfm_io import match_descriptors  # noqa: F401  (in front of it: descriptors to a store)
 from sfm_io import match_descriptors_guided  # noqa: F401  (behind verify_pairs: rematch_verified)
 from sfm_two_view import projection
