@@ -10,8 +10,9 @@
 // Every term is below 2^22 in magnitude, so the int32 accumulation is exact.
 //
 //   k_md_norms   ||a'||^2 of every keypoint, 16 bytes per thread.
-//   k_md_nn      (in match_common.hpp: retrieval.hip instantiates it too)
-//                a workgroup of 4 waves owns MD_BM = 128 rows of the pair's
+//   k_md_nn      (in match_common.hpp, the one nearest-neighbour kernel: guided
+//                matching instantiates it with its gate, retrieval.hip as here)
+//                a workgroup of 4 waves owns md_bm = 128 rows of the pair's
 //                first image: each wave keeps the A fragments of its 32 rows in
 //                registers for the whole kernel (lane l: row l & 15, bytes
 //                16 (l >> 4) .. + 15 of each 64-byte k step).  The second
@@ -48,94 +49,6 @@ extern "C" int sfm_match_descriptors(const uint8_t *desc, int64_t n_kp, const in
                                      int32_t cross_check, int64_t capacity, int64_t *match_start, int32_t *match_a,
                                      int32_t *match_b, int32_t *match_dsq, int32_t *nn, int32_t *d1, int32_t *d2,
                                      int32_t *nn_rev, int device) {
-    MdPlan plan;
-    SFM_TRY(md_plan(desc, n_kp, img_start, n_images, dim, pairs, P, ratio, max_dsq, cross_check, capacity, match_start,
-                    match_a, match_b, match_dsq, plan));
-    const int64_t *row_off = plan.row_off(), *col_off = plan.col_off();
-    const int64_t max_i = plan.max_i, max_j = plan.max_j;
-    const double ratio_sq = ratio * ratio;
-
-    match_start[0] = 0;
-    if (P == 0) return 0;
-    const int64_t n_rows = row_off[P], n_cols = col_off[P];
-    const bool reverse = cross_check || nn_rev;
-
-    ThreadCtx *c = thread_ctx(device);
-    if (!c) return SFM_ERR_HIP;
-    hipStream_t s = c->stream;
-    size_t tmp_bytes = 0;
-    SFM_TRY(md_scan_bytes(n_rows, s, tmp_bytes));
-
-    Pack in(c->buf[0]), out(c->buf[1]), work(c->buf[2]);
-    const auto i_desc = in.add<uint8_t>(n_kp * dim);
-    const auto i_is = in.add<int64_t>(n_images + 1);
-    const auto i_pairs = in.add<int32_t>(2 * P);
-    const auto i_ro = in.add<int64_t>(P + 1), i_co = in.add<int64_t>(P + 1);
-    const auto o_ms = out.add<int64_t>(P + 1);
-    const auto o_a = out.add<int32_t>(n_rows), o_b = out.add<int32_t>(n_rows), o_dsq = out.add<int32_t>(n_rows);
-    const auto o_nn = out.add<int32_t>(n_rows), o_d1 = out.add<int32_t>(n_rows), o_d2 = out.add<int32_t>(n_rows);
-    const auto o_rev = out.add<int32_t>(reverse ? n_cols : 0);
-    const auto w_norm = work.add<int32_t>(n_kp);
-    const auto w_flag = work.add<int32_t>(n_rows + 1);  // a last 0, so that the scan's last entry is the total
-    const auto w_place = work.add<int64_t>(n_rows + 1);
-    const auto w_tmp = work.add<char>(tmp_bytes);
-    SFM_TRY(in.reserve());
-    SFM_TRY(out.reserve());
-    SFM_TRY(work.reserve());
-
-    CallTimer tm(c);
-    SFM_TRY(tm.mark(s));
-    SFM_TRY(in.upload(i_desc, desc, s));
-    SFM_TRY(in.upload(i_is, img_start, s));
-    SFM_TRY(in.upload(i_pairs, pairs, s));
-    SFM_TRY(in.upload(i_ro, row_off, s));
-    SFM_TRY(in.upload(i_co, col_off, s));
-    SFM_TRY(tm.mark(s));
-
-    const unsigned gy = (unsigned)(P < 65535 ? P : 65535);
-    const uint8_t *d_desc = in.ptr(i_desc);
-    const int64_t *d_is = in.ptr(i_is), *d_ro = in.ptr(i_ro), *d_co = in.ptr(i_co);
-    const int32_t *d_pairs = in.ptr(i_pairs);
-    int32_t *d_norm = work.ptr(w_norm);
-    int32_t *d_nn = out.ptr(o_nn), *d_d1 = out.ptr(o_d1), *d_d2 = out.ptr(o_d2);
-    int32_t *d_rev = reverse ? out.ptr(o_rev) : nullptr;
-    if (n_kp > 0) {
-        const dim3 g_norm((unsigned)ceil_div(n_kp * (dim / 16), MD_THREADS));
-#define MD_NORMS(D) MD_LAUNCH(k_md_norms<D>, g_norm, d_desc, n_kp, d_norm)
-        MD_BY_DIM(MD_NORMS);
-#undef MD_NORMS
-    }
-    if (max_i > 0) {
-        const dim3 g_fwd((unsigned)ceil_div(max_i, MD_BM), gy);
-#define MD_FWD(D) MD_LAUNCH((k_md_nn<D, false>), g_fwd, d_desc, d_norm, d_is, d_pairs, P, d_ro, d_nn, d_d1, d_d2)
-        MD_BY_DIM(MD_FWD);
-#undef MD_FWD
-    }
-    if (reverse && max_j > 0) {
-        const dim3 g_rev((unsigned)ceil_div(max_j, MD_BM), gy);
-#define MD_REV(D)                                                                                    \
-    MD_LAUNCH((k_md_nn<D, true>), g_rev, d_desc, d_norm, d_is, d_pairs, P, d_co, d_rev, (int32_t *)nullptr, \
-              (int32_t *)nullptr)
-        MD_BY_DIM(MD_REV);
-#undef MD_REV
-    }
-    SFM_TRY(md_compact(s, P, max_i, n_rows, d_is, d_pairs, d_ro, d_co, d_nn, d_d1, d_d2,
-                       cross_check ? (const int32_t *)d_rev : (const int32_t *)nullptr, ratio_sq, max_dsq,
-                       work.ptr(w_flag), work.ptr(w_place), work.ptr(w_tmp), tmp_bytes, out.ptr(o_ms), out.ptr(o_a),
-                       out.ptr(o_b), out.ptr(o_dsq)));
-    SFM_TRY(tm.mark(s));
-
-    // match_start first: its last entry sizes the other copies
-    SFM_TRY(out.download(match_start, o_ms, s));
-    SFM_HIP(hipStreamSynchronize(s));
-    const size_t total = (size_t)match_start[P];
-    SFM_TRY(out.download(match_a, o_a, 0, total, s));
-    SFM_TRY(out.download(match_b, o_b, 0, total, s));
-    SFM_TRY(out.download(match_dsq, o_dsq, 0, total, s));
-    SFM_TRY(out.download(nn, o_nn, s));
-    SFM_TRY(out.download(d1, o_d1, s));
-    SFM_TRY(out.download(d2, o_d2, s));
-    SFM_TRY(out.download(nn_rev, o_rev, s));
-    SFM_TRY(tm.finish(s));
-    return 0;
+    return md_run<MdNoGate>(desc, n_kp, img_start, n_images, dim, pairs, P, ratio, max_dsq, cross_check, capacity,
+                            match_start, match_a, match_b, match_dsq, nn, d1, d2, nn_rev, MdGateIn(), device);
 }

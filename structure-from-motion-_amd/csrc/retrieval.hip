@@ -6,7 +6,7 @@
 // Everything is integer work except the score (include/sfmcore.h).
 //
 // sfm_vocab_train
-//   k_md_norms, k_md_nn   the matcher's kernels (match_common.hpp), unchanged:
+//   k_md_norms, k_md_nn   the matcher's kernels (match_common.hpp), no gate:
 //                the centres are appended to the descriptors as one more
 //                "image", the descriptor rows are cut into pseudo-images of at
 //                most MD_MAX_KP rows, and every pseudo-image is paired with the
@@ -385,7 +385,7 @@ extern "C" int sfm_vocab_train(const uint8_t *desc, int64_t n, int32_t dim, int3
     int32_t *d_norm = work.ptr(w_norm), *d_word = out.ptr(o_word), *d_dsq = work.ptr(w_dsq);
     int32_t *d_changed = work.ptr(w_changed);
     u64 *d_count = out.ptr(o_count), *d_inertia = out.ptr(o_inertia);
-    const dim3 g_nn((unsigned)ceil_div(max_i, MD_BM), (unsigned)(P < 65535 ? P : 65535));
+    const dim3 g_nn((unsigned)ceil_div(max_i, md_bm<MdNoGate>(dim)), (unsigned)(P < 65535 ? P : 65535));
     const dim3 g_tally((unsigned)(ceil_div(n, MD_THREADS) < 4096 ? ceil_div(n, MD_THREADS) : 4096));
     const dim3 g_update((unsigned)ceil_div(n_bytes, MD_THREADS));
     SFM_HIP(hipMemsetAsync(d_inertia, 0, o_inertia.bytes(), s));
@@ -397,14 +397,13 @@ extern "C" int sfm_vocab_train(const uint8_t *desc, int64_t n, int32_t dim, int3
         const dim3 g_norm((unsigned)ceil_div(rows * (dim / 16), MD_THREADS));
         const uint8_t *nd = d_desc + first * dim;
         int32_t *nn = d_norm + first;
-#define VT_NORMS(D) MD_LAUNCH(k_md_norms<D>, g_norm, nd, rows, nn)
-        MD_BY_DIM(VT_NORMS);
-#undef VT_NORMS
-#define VT_NN(D)                                                                                       \
-    MD_LAUNCH((k_md_nn<D, false>), g_nn, (const uint8_t *)d_desc, (const int32_t *)d_norm, d_is, d_pairs, P, d_is, \
-              d_word, d_dsq, (int32_t *)nullptr)
-        MD_BY_DIM(VT_NN);
-#undef VT_NN
+        SFM_TRY(md_by_dim(dim, [&](auto D) -> int {
+            MD_LAUNCH(k_md_norms<D()>, g_norm, nd, rows, nn);
+            MD_LAUNCH((k_md_nn<D(), false, MdNoGate>), g_nn, (const uint8_t *)d_desc, (const int32_t *)d_norm, d_is,
+                      d_pairs, P, d_is, d_word, d_dsq, (int32_t *)nullptr, (const double2 *)nullptr,
+                      (const double *)nullptr, 0.0, (int32_t *)nullptr);
+            return 0;
+        }));
         SFM_HIP(hipMemsetAsync(d_count, 0, o_count.bytes(), s));
         MD_LAUNCH(k_vt_tally, g_tally, (const int32_t *)d_word, (const int32_t *)d_dsq, n, d_count, d_inertia + t);
         return 0;
@@ -419,10 +418,11 @@ extern "C" int sfm_vocab_train(const uint8_t *desc, int64_t n, int32_t dim, int3
         SFM_TRY(cam_major_sort(work.ptr(w_tmp), tmp_bytes, d_word, d_key, d_perm, n, n_words, s));
         const int per_block = MD_THREADS / (dim / 4) * VT_ROWS;
         const dim3 g_sums((unsigned)ceil_div(n, per_block));
-#define VT_SUMS(D) \
-    MD_LAUNCH(k_vt_sums<D>, g_sums, (const uint8_t *)d_desc, (const uint32_t *)d_key, (const int32_t *)d_perm, n, d_sums)
-        MD_BY_DIM(VT_SUMS);
-#undef VT_SUMS
+        SFM_TRY(md_by_dim(dim, [&](auto D) -> int {
+            MD_LAUNCH(k_vt_sums<D()>, g_sums, (const uint8_t *)d_desc, (const uint32_t *)d_key,
+                      (const int32_t *)d_perm, n, d_sums);
+            return 0;
+        }));
         MD_LAUNCH(k_vt_update, g_update, d_centres, (const uint32_t *)d_sums, (const u64 *)d_count, n_bytes, dim,
                   d_changed + T);
         int32_t changed = 0;

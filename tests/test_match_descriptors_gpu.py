@@ -13,8 +13,8 @@ import test_match_descriptors as md
 from test_match_descriptors import INT32_MAX
 
 pytestmark = pytest.mark.gpu
-T = 64    # the kernel's column tile (MD_TN of csrc/match_descriptors.hip)
-BM = 128  # the rows of one workgroup (MD_BM)
+T = 64    # the kernel's column tile (MD_TN of csrc/match_common.hpp)
+BM = 128  # the rows of one workgroup (md_bm)
 
 
 @pytest.fixture(scope="module")

@@ -14,7 +14,7 @@ from test_match_descriptors import INT32_MAX
 
 pytestmark = pytest.mark.gpu
 T = 64    # the kernel's column tile (MD_TN of csrc/match_common.hpp)
-BM = 128  # the rows of one workgroup at dim 64 and 128 (MD_BM); 64 at dim 256
+BM = 128  # the rows of one workgroup at dim 64 and 128 (md_bm); 64 at dim 256
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ from test_retrieval import N_WORDS, SELECT_OUTPUTS, TRAIN_OUTPUTS
 
 pytestmark = pytest.mark.gpu
 T = 64    # the nearest-centre kernel's column tile (MD_TN of csrc/match_common.hpp)
-BM = 128  # the rows of one workgroup (MD_BM)
+BM = 128  # the rows of one workgroup (md_bm)
 
 
 @pytest.fixture(scope="module")
