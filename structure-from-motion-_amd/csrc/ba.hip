@@ -69,7 +69,7 @@ struct LocalGroup {
     std::vector<double> result;
     int refs = 0;
     bool aborted = false;  // a rank failed: the others stop waiting and return SFM_ERR_COMM
-    // In-process ranks share one GPU: their persistent solves (gj_solve.hpp)
+    // In-process ranks share one GPU: their persistent solves (gjr_solve.hpp)
     // run one after another (each launch waits for the previous rank's), so
     // two spinning grids never compete for the CUs.
     std::mutex solve_mu;
@@ -1901,8 +1901,7 @@ struct CamTrialArgs {  // k_chol_backsolve's epilogue (nc = 0: none)
     double *Rt_new, *cam_out;
 };
 
-#include "gj_solve.hpp"   // the persistent block Gauss-Jordan solve (one launch), segment layout
-#include "gjr_solve.hpp"  // ... and its row-distributed form (default since round 4)
+#include "gjr_solve.hpp"  // the persistent block Gauss-Jordan solve (one launch; the default)
 
 template <int TB>
 __global__ void __launch_bounds__(SOLVE_THREADS) k_chol_backsolve(double *__restrict__ A, int32_t nsp,
@@ -2202,55 +2201,11 @@ static int launch_reduced_solve(int32_t ns, int32_t nsp, const double *payload, 
     return launch_cholesky(payload, ns, lam, A, nsp, b, D, bad, s, tb, gate, ct, src, dpp);
 }
 
-// Persistent Gauss-Jordan solve (gj_solve.hpp): the workgroup layout for
-// nT tiles.  cb = 0: the grid would not fit one workgroup per CU, so the
-// multi-launch Cholesky above runs instead (SFM_SOLVE=chol forces it).
-struct GjPlan {
-    int cb = 0, nseg = 0, ncb = 0;
-    int grid() const { return cb ? ncb * nseg : 0; }
-};
-static GjPlan gj_plan(int nT, int ncu) {
-    GjPlan g;
-    if (const char *e = std::getenv("SFM_SOLVE"))
-        if (std::strcmp(e, "chol") == 0) return g;
-    if (nT > gj::NTMAX) return g;
-    const int nseg = (nT + gj::SR - 1) / gj::SR;
-    for (int cb : {gj::SR, 2 * gj::SR}) {
-        const int ncb = (nT + cb - 1) / cb;
-        if (ncb * nseg <= ncu) {
-            g.cb = cb;
-            g.nseg = nseg;
-            g.ncb = ncb;
-            break;
-        }
-    }
-    return g;
-}
 static int device_cus(int device) {
     int n = 0;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
     return n;
 }
-
-// device buffers of one solver instance: panels, L / y copies, flags (zeroed
-// once; epochs only grow), abort word, arrival counter
-struct GjBufs {
-    double *G = nullptr, *L = nullptr, *Y = nullptr;
-    int *flag = nullptr, *err = nullptr;
-    unsigned *arrive = nullptr;
-    static size_t doubles(int nT, int nseg) {
-        return (size_t)nT * nT * 16 * 16 + (size_t)nT * nseg * (256 + 16);
-    }
-    static size_t ints(int nT, int nseg) { return (size_t)nT * nseg + 64; }
-    void carve(double *d, int *i, int nT, int nseg) {
-        G = d;
-        L = G + (size_t)nT * nT * 16 * 16;
-        Y = L + (size_t)nT * nseg * 256;
-        flag = i;
-        err = i + (size_t)nT * nseg;
-        arrive = reinterpret_cast<unsigned *>(i + (size_t)nT * nseg + 32);
-    }
-};
 
 // SFM_SWEEP_STAMPS=1: k_schur_sweep records s_memrealtime stamps per
 // (workgroup, event, wave) into a process-wide device buffer (sfm_sweep_debug
@@ -2283,7 +2238,7 @@ static long long *gj_dbg_ptr() {
     static const bool on = std::getenv("SFM_GJ_DEBUG") && std::atoi(std::getenv("SFM_GJ_DEBUG")) != 0;
     if (!on) return nullptr;
     if (!g_gj_dbg) {
-        g_gj_dbg_n = (size_t)256 * (gj::NTMAX + 1) * 16;
+        g_gj_dbg_n = (size_t)256 * (gjr::NTMAX + 1) * 16;
         if (hipMalloc(&g_gj_dbg, g_gj_dbg_n * sizeof(long long)) != hipSuccess) return g_gj_dbg = nullptr;
         (void)hipMemset(g_gj_dbg, 0, g_gj_dbg_n * sizeof(long long));
     }
@@ -2297,39 +2252,10 @@ extern "C" int sfm_gj_debug(long long *out, int64_t n) {
     return 0;
 }
 
-static int launch_gj(const GjPlan &g, int nT, int32_t ns, const double *payload, const double *lam, const GjBufs &b, int epoch, double *x, int *bad, const int *gate,
-                     const CamTrialArgs &ct, hipStream_t s, const double *payload_spec = nullptr,
-                     const int *use_spec = nullptr) {
-    gj::Args a;
-    a.payload = payload;
-    a.payload_spec = payload_spec;
-    a.use_spec = use_spec;
-    a.ns = ns;
-    a.nT = nT;
-    a.cb = g.cb;
-    a.nseg = g.nseg;
-    a.lam = lam;
-    a.gate = gate;
-    a.Gp = b.G;
-    a.Lp = b.L;
-    a.Yp = b.Y;
-    a.flag = b.flag;
-    a.epoch = epoch;
-    a.x = x;
-    a.bad = bad;
-    a.err = b.err;
-    a.arrive = b.arrive;
-    a.ct = ct;
-    a.dbg = gj_dbg_ptr();
-    hipLaunchKernelGGL(gj::k_gj_solve, dim3(g.grid()), dim3(gj::THREADS), 0, s, a);
-    SFM_HIP(hipGetLastError());
-    return 0;
-}
-
-// Row-distributed persistent solve (gjr_solve.hpp): one workgroup per tile
+// Persistent Gauss-Jordan solve (gjr_solve.hpp): one workgroup per tile
 // row, all resident at once (every wait is bounded, and the host checks the
-// occupancy against the grid).  tpw = 0: not applicable, the segment layout
-// above (or the Cholesky) runs instead; SFM_SOLVE=gjseg / chol force those.
+// occupancy against the grid).  tpw = 0: not applicable, the multi-launch
+// Cholesky above runs instead; SFM_SOLVE=chol forces that.
 struct GjrPlan {
     int nT = 0, tpw = 0;
     bool ok() const { return tpw > 0; }
@@ -2351,7 +2277,7 @@ static bool gjr_resident(int nT, int ncu) {
 static GjrPlan gjr_plan(int nT, int ncu) {
     GjrPlan g;
     if (const char *e = std::getenv("SFM_SOLVE"))
-        if (std::strcmp(e, "chol") == 0 || std::strcmp(e, "gjseg") == 0) return g;
+        if (std::strcmp(e, "chol") == 0) return g;
     // tile slots per U wave: 4 or TREG in registers (up to 28 / 77 tile
     // rows), past that TREG_L + TLDS_L (the latter in LDS: up to gjr::NTMAX = 128)
     if (nT < 1 || nT > gjr::NTMAX || nT > ncu) return g;
@@ -3941,11 +3867,8 @@ struct sfm_ba_problem {
     hipEvent_t ev[2 * T_NT] = {};
     hipEvent_t ev_it[2 * T_NT * kEvSlots] = {};  // per-iteration timing slots of a batch
     LMState *d_lm = nullptr;
-    // persistent Gauss-Jordan reduced solve (gj_solve.hpp)
-    GjPlan gjp;
-    GjBufs gjb;
-    int gj_epoch = 0;
-    GjrPlan gjrp;  // the row-distributed solve (default; gjp is then unused)
+    // persistent Gauss-Jordan reduced solve (gjr_solve.hpp; !gjrp.ok(): the Cholesky runs)
+    GjrPlan gjrp;
     GjrBufs gjrb;
     unsigned gjr_tag = 0;
     bool gjr_fold = false;  // fold k_schur_finish into the row-distributed solve (SFM_GJR_FOLD)
@@ -4607,7 +4530,6 @@ static int ba_create(int32_t nc, int64_t np_, int64_t no, const int32_t *cam, co
         (rc = p->alloc(p->d_nbig, 1)) || (rc = p->alloc(p->d_gbuf, 6 * (int64_t)nc + 1)))
         return rc;
     p->gjrp = p->tb == 16 ? gjr_plan(p->nT, device_cus(device)) : GjrPlan{};
-    p->gjp = p->tb == 16 && !p->gjrp.ok() ? gj_plan(p->nT, device_cus(device)) : GjPlan{};
     p->bs_cl_blocks = backsub_cl_blocks(nc, device_cus(device), p->pt_blocks);
     p->lin_cl_blocks = linearize_cl_blocks(nc, device_cus(device), p->pt_blocks);
     // Speculation (one rank, a persistent solve): second copies of what the
@@ -4617,9 +4539,9 @@ static int ba_create(int32_t nc, int64_t np_, int64_t no, const int32_t *cam, co
     // sub-ranges each (SweepSplit).  Every copy is written by the chain
     // before anything reads it, like d_Lq / d_slab / d_payload themselves.
     std::vector<int32_t> sp_split_of;  // (lives until the upload's stream sync below)
-    if (!p->comm && (p->gjrp.ok() || p->gjp.cb) && !sw.split_S && sw.nrange <= NXCD) {
+    if (!p->comm && p->gjrp.ok() && !sw.split_S && sw.nrange <= NXCD) {
         const int ncu = device_cus(device);
-        const int nwg = p->gjrp.ok() ? p->gjrp.nT : p->gjp.grid();
+        const int nwg = p->gjrp.nT;
         // Workgroups go to the XCDs round-robin, the solve's as the sweep's, and
         // an XCD's workgroup past its free CUs waits for one, a whole item's
         // span: so NXCD times the free CUs of the fullest XCD, not ncu - nwg
@@ -4672,16 +4594,6 @@ static int ba_create(int32_t nc, int64_t np_, int64_t no, const int32_t *cam, co
         p->gjrb.carve(gw, gi, p->nT);
         SFM_HIP(hipMemsetAsync(gw, 0, GjrBufs::words(p->nT) * sizeof(gjr::u64), p->stream));
         SFM_HIP(hipMemsetAsync(gi, 0, GjrBufs::ints * sizeof(int), p->stream));
-        if (!p->ev_solve) SFM_HIP(hipEventCreateWithFlags(&p->ev_solve, hipEventDisableTiming));
-    }
-    if (p->gjp.cb) {
-        double *gd = nullptr;
-        int *gi = nullptr;
-        if ((rc = p->alloc(gd, (int64_t)GjBufs::doubles(p->nT, p->gjp.nseg))) ||
-            (rc = p->alloc(gi, (int64_t)GjBufs::ints(p->nT, p->gjp.nseg))))
-            return rc;
-        p->gjb.carve(gd, gi, p->nT, p->gjp.nseg);
-        SFM_HIP(hipMemsetAsync(gi, 0, GjBufs::ints(p->nT, p->gjp.nseg) * sizeof(int), p->stream));
         if (!p->ev_solve) SFM_HIP(hipEventCreateWithFlags(&p->ev_solve, hipEventDisableTiming));
     }
     ctick("alloc");
@@ -5113,11 +5025,10 @@ static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par, int it) {
                        camlin_args(p, true, &p->d_lm[par].run_lin), sw_dbg_ptr(), p->d_sw_err, p->sw_split);
     SFM_HIP(hipGetLastError());
     // one rank: the solve's first launch sums the slabs itself (SlabSrc)
-    // (the persistent solve reads the finished payload: the finish runs as its own launch)
-    // (the row-distributed solve only with SFM_GJR_FOLD=1: its prologue then
+    // (the persistent solve only with SFM_GJR_FOLD=1: its prologue then
     // reads 8 range slabs per element while the chain runs, cfg5 solve 0.457
     // -> 0.523 ms against the finish's 0.028 ms, round 4)
-    const bool fin_fused = !p->comm && p->fin_fused && !p->gjp.cb && (!p->gjrp.ok() || p->gjr_fold);
+    const bool fin_fused = !p->comm && p->fin_fused && (!p->gjrp.ok() || p->gjr_fold);
     if (!fin_fused) {
         hipLaunchKernelGGL(k_schur_finish, dim3(ceil_div(p->sw_nbd * ITEM_W, FIN_THREADS)), dim3(FIN_THREADS), 0, s, p->ns, p->sw_nbd, p->sw_nrange,
                            p->d_sw_blkij, p->d_slab, p->d_camlin, p->d_payload, greal, p->d_sw_split_of, p->sw_split);
@@ -5138,19 +5049,15 @@ static int run_step(sfm_ba_problem *p, hipEvent_t *ev, int par, int it) {
     const CamTrialArgs ct = {p->nc, p->ns, p->d_payload, lam, p->d_Rt, p->d_Rt2, p->d_scal + 4};
     const SlabSrc src = fin_fused ? SlabSrc{p->d_slab, p->d_camlin, p->sw_nbd, p->sw_nrange, p->sw_split, p->d_sw_split_of}
                                   : SlabSrc{nullptr, nullptr, 0, 0, {}, nullptr};
-    if (p->gjp.cb || p->gjrp.ok()) {
+    if (p->gjrp.ok()) {
         LocalGroup *lg = p->comm ? p->comm->local : nullptr;
         std::unique_lock<std::mutex> lk;
         if (lg) {  // in-process ranks on one GPU: one persistent solve at a time
             lk = std::unique_lock<std::mutex>(lg->solve_mu);
             if (lg->last_solve) SFM_HIP(hipStreamWaitEvent(s, lg->last_solve, 0));
         }
-        if (p->gjrp.ok()) {
-            if ((rc = launch_gjr(p->gjrp, p->ns, p->d_payload, lam, p->gjrb, ++p->gjr_tag, p->d_b, bad, gst, ct, s,
-                                 src, pay_spec, use_spec)))
-                return rc;
-        } else if ((rc = launch_gj(p->gjp, p->nT, p->ns, p->d_payload, lam, p->gjb, ++p->gj_epoch, p->d_b, bad,
-                                   gst, ct, s, pay_spec, use_spec)))
+        if ((rc = launch_gjr(p->gjrp, p->ns, p->d_payload, lam, p->gjrb, ++p->gjr_tag, p->d_b, bad, gst, ct, s, src,
+                             pay_spec, use_spec)))
             return rc;
         // the solve's workgroups are queued: now the speculative chain beside them
         if (p->spec_armed && (rc = run_spec_chain(p, par, it, timed))) return rc;
@@ -5250,12 +5157,8 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
     for (int k = 0; k < kHostRing; ++k) __atomic_store_n(&p->h_ring[k].seq, 0, __ATOMIC_RELAXED);
     hipLaunchKernelGGL(k_lm_reset, dim3(1), dim3(1), 0, s, p->d_lm, o->initial_lambda, p->d_bad);
     SFM_HIP(hipGetLastError());
-    // the persistent solves' error and arrival words start clean every solve
+    // the persistent solve's error and arrival words start clean every solve
     // (an aborted launch may have left an arrival count behind)
-    if (p->gjp.cb) {
-        SFM_HIP(hipMemsetAsync(p->gjb.err, 0, sizeof(int), s));
-        SFM_HIP(hipMemsetAsync(p->gjb.arrive, 0, sizeof(unsigned), s));
-    }
     if (p->gjrp.ok()) SFM_HIP(hipMemsetAsync(p->gjrb.err, 0, GjrBufs::ints * sizeof(int), s));
     SFM_HIP(hipMemsetAsync(p->d_sw_err, 0, sizeof(int), s));
     auto account = [&](int j) {  // per-phase event times of iteration j (complete once its state is published)
@@ -5319,7 +5222,6 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
     LMState h{};
     int gj_err = 0;
     SFM_HIP(hipMemcpyAsync(&h, p->d_lm + (it & 1), sizeof h, hipMemcpyDeviceToHost, s));
-    if (p->gjp.cb) SFM_HIP(hipMemcpyAsync(&gj_err, p->gjb.err, sizeof gj_err, hipMemcpyDeviceToHost, s));
     if (p->gjrp.ok()) SFM_HIP(hipMemcpyAsync(&gj_err, p->gjrb.err, sizeof gj_err, hipMemcpyDeviceToHost, s));
     int sw_err = 0;
     SFM_HIP(hipMemcpyAsync(&sw_err, p->d_sw_err, sizeof sw_err, hipMemcpyDeviceToHost, s));
@@ -5350,23 +5252,8 @@ extern "C" int sfm_ba_solve(sfm_ba_problem *p, const sfm_ba_opts *o, sfm_ba_repo
 }
 
 // Diagnostic entry: solves the SPD system S x = rhs (n x n, row-major) with
-// the reduced-camera solver of sfm_ba_solve (tiled Cholesky).
-// Diagnostic: the published panels of this thread's last persistent reduced
-// solve (sfm_reduced_solve): G [nT][nsp][16], L [nT][nseg][256], y [nT][nseg][16].
-extern "C" int sfm_gj_dump(double *G, double *L, double *Y, int32_t nT, int32_t nseg, int device) {
-    SFM_CHECK_ARG(G && L && Y, "null pointer");
-    ThreadCtx *c = thread_ctx(device);
-    if (!c) return SFM_ERR_HIP;
-    SFM_CHECK_ARG(c->buf[5].bytes >= GjBufs::doubles(nT, nseg) * sizeof(double), "no such solve");
-    GjBufs b;
-    b.carve(c->buf[5].as<double>(), c->buf[6].as<int>(), nT, nseg);
-    SFM_HIP(hipStreamSynchronize(c->stream));
-    SFM_HIP(hipMemcpy(G, b.G, (size_t)nT * nT * 256 * sizeof(double), hipMemcpyDeviceToHost));
-    SFM_HIP(hipMemcpy(L, b.L, (size_t)nT * nseg * 256 * sizeof(double), hipMemcpyDeviceToHost));
-    SFM_HIP(hipMemcpy(Y, b.Y, (size_t)nT * nseg * 16 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-
+// the reduced-camera solver of sfm_ba_solve (the persistent Gauss-Jordan where
+// its plan applies, else the tiled Cholesky).
 extern "C" int sfm_reduced_solve(const double *S, const double *rhs, int32_t n, double *x, int device) {
     SFM_CHECK_ARG(S && rhs && x, "null pointer");
     SFM_CHECK_ARG(n >= 1, "n < 1");
@@ -5375,7 +5262,6 @@ extern "C" int sfm_reduced_solve(const double *S, const double *rhs, int32_t n, 
     const int tb = chol_tile(n);
     const int32_t nsp = (n + tb - 1) / tb * tb;
     const GjrPlan gjrp = tb == 16 ? gjr_plan(nsp / 16, device_cus(device)) : GjrPlan{};
-    const GjPlan gjp = tb == 16 && !gjrp.ok() ? gj_plan(nsp / 16, device_cus(device)) : GjPlan{};
     int rc;
     const size_t pb = (size_t)pay_vec_base(n);
     if ((rc = c->buf[0].reserve((pb + 3 * (size_t)n + 1) * sizeof(double))) ||
@@ -5410,38 +5296,6 @@ extern "C" int sfm_reduced_solve(const double *S, const double *rhs, int32_t n, 
         SFM_HIP(hipMemsetAsync(c->buf[2].p, 0, (size_t)nsp * sizeof(double), c->stream));
         if ((rc = launch_gjr(gjrp, n, d_pay, d_pay + pb + 3 * (size_t)n, b, ++c->gjr_tag, c->buf[2].as<double>(),
                              c->buf[4].as<int>(), nullptr, CamTrialArgs{}, c->stream)))
-            return rc;
-        int err = 0;
-        SFM_HIP(hipMemcpyAsync(&err, b.err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        SFM_HIP(hipStreamSynchronize(c->stream));
-        if (err) {
-            set_error("reduced solve: the persistent solve timed out");
-            return SFM_ERR_HIP;
-        }
-    } else if (gjp.cb) {
-        const int nT = nsp / 16;
-        const size_t nint = GjBufs::ints(nT, gjp.nseg);
-        if ((rc = c->buf[5].reserve(GjBufs::doubles(nT, gjp.nseg) * sizeof(double))) ||
-            (rc = c->buf[6].reserve(nint * sizeof(int))))
-            return rc;
-        // fresh flags: zero them once, epochs restart.  A regrown buffer can
-        // come back at the same address, and a new layout moves the flags
-        // and the arrival word: either way the old words mean nothing
-        if (c->buf[6].p != c->gj_ints || c->gj_nT != nT || c->gj_nseg != gjp.nseg) {
-            SFM_HIP(hipMemsetAsync(c->buf[6].p, 0, c->buf[6].bytes, c->stream));
-            c->gj_ints = c->buf[6].p;
-            c->gj_nT = nT;
-            c->gj_nseg = gjp.nseg;
-            c->gj_epoch = 0;
-        }
-        GjBufs b;
-        b.carve(c->buf[5].as<double>(), c->buf[6].as<int>(), nT, gjp.nseg);
-        SFM_HIP(hipMemsetAsync(b.err, 0, sizeof(int), c->stream));
-        SFM_HIP(hipMemsetAsync(b.arrive, 0, sizeof(unsigned), c->stream));  // an aborted launch may have left a count
-        SFM_HIP(hipMemsetAsync(c->buf[2].p, 0, (size_t)nsp * sizeof(double), c->stream));
-        if ((rc = launch_gj(gjp, nT, n, d_pay, d_pay + pb + 3 * (size_t)n, b,
-                            ++c->gj_epoch, c->buf[2].as<double>(), c->buf[4].as<int>(), nullptr, CamTrialArgs{},
-                            c->stream)))
             return rc;
         int err = 0;
         SFM_HIP(hipMemcpyAsync(&err, b.err, sizeof(int), hipMemcpyDeviceToHost, c->stream));

@@ -1,14 +1,27 @@
-// Row-distributed persistent block Gauss-Jordan solve of the damped reduced
-// camera system (S + lambda clamp(diag U)) x = b in ONE launch (round 4).
-// Replaces the reference's MINPACK dense QR step on the BA hot path
-// (Phase 1/BundleAdjustment.py:205-212, via scipy lmdif); included by ba.hip
-// after gj_solve.hpp (the 16-pivot DPP tile factor, elem_ref, cam_trial).
+// Persistent block Gauss-Jordan solve of the damped reduced camera system
+// (S + lambda clamp(diag U)) x = b in ONE launch, one workgroup per tile row
+// (round 4).  Replaces the reference's MINPACK dense QR step on the BA hot
+// path (Phase 1/BundleAdjustment.py:205-212, via scipy lmdif); included by
+// ba.hip after the assembly helpers (SlabSrc, assembled_src) and
+// CamTrialArgs.
 //
-// The algorithm is gj_solve.hpp's block Gauss-Jordan with Cholesky pivots
-// (step p: L_p = chol(A_pp), G_i = A_ip L_p^-T for every row tile i != p,
-// A_ij -= G_i G_j^T for j > p, b_i -= G_i y_p; at the end x_i = L_i^-T L_i^-1
-// b_i), laid out so that the critical path crosses ONE workgroup boundary per
-// pivot and nothing else:
+// Why Gauss-Jordan: a tiled Cholesky needs nT = nsp / 16 dependent column
+// steps for the factor and as many again for the back substitution.  As one
+// launch per column (k_chol_col) each step costs a kernel boundary plus a
+// round of cross-XCD tile loads (~5.4 us at cfg4); the back substitution is
+// a further serial chain.  Block Gauss-Jordan with Cholesky pivots
+//   step p:  L_p = chol(A_pp);  G_i = A_ip L_p^-T (every row tile i != p);
+//            y_p = L_p^-1 b_p;  A_ij -= G_i G_j^T (j > p);  b_i -= G_i y_p
+//   end:     x_i = L_i^-T L_i^-1 b_i   (block diagonal left over)
+// has no back substitution at all (its extra flops are off the critical
+// path), and every step's dependency is only "column p+1 updated by panel
+// p".  A_pj (j > p) is never read: the trailing matrix is symmetric, so
+// L_p^-1 A_pj = G_j^T.  Rows above the pivot (already pivoted) keep being
+// updated; a tile (i, j) with p < i < j (the mirror of (j, i)) is not kept
+// and is imported when row i becomes pivoted: A_ij = L_i G_j^T.
+//
+// The layout makes the critical path cross ONE workgroup boundary per pivot
+// and nothing else:
 //
 //  * workgroup r owns row tile r ("owner r"): the tiles A_rj of its row that
 //    are still live (j <= r before its pivot: the lower triangle; j > p after
@@ -390,6 +403,32 @@ __device__ __forceinline__ double gy(const d4 &g, double yl, int lane) {
     return s;
 }
 
+// element (I, J) of S + lambda clamp(diag U) from the payload, the lower
+// triangle mirrored (what a Cholesky of S reads), identity on the padding;
+// the loads are issued by the caller (batched)
+struct ElemRef {
+    int64_t idx, dg;  // payload index of S_IJ (-1: padding), of diag U_I (-1: off-diagonal)
+    double pad;       // value on the padding
+};
+__device__ __forceinline__ ElemRef elem_ref(int32_t ns, int I, int J) {
+    if (I < J) {
+        const int t = I;
+        I = J;
+        J = t;
+    }
+    ElemRef r;
+    if (I < ns && J < ns) {
+        r.idx = pay_index(ns, I, J);
+        r.dg = I == J ? pay_vec_base(ns) + I : -1;
+        r.pad = 0.0;
+    } else {
+        r.idx = -1;
+        r.dg = -1;
+        r.pad = I == J ? 1.0 : 0.0;
+    }
+    return r;
+}
+
 // tile A_rj of the damped, identity-padded system, held as the accumulator
 // of A_rj^T: element e of lane l = A(16 r + (l & 15), 16 j + (l >> 4) + 4e)
 // a strictly lower tile (j <= r - 2: no diagonal element, no damping) of the
@@ -425,10 +464,10 @@ __device__ __forceinline__ d4 load_tile(const Args &a, double lambda, int r, int
             v[e] = assembled_src(a.src, a.payload, a.ns, lambda, TL * r + (lane & 15), TL * j + (lane >> 4) + 4 * e);
         return v;
     }
-    gj::ElemRef er[4];
+    ElemRef er[4];
     double v[4], dg[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) er[e] = gj::elem_ref(a.ns, TL * r + (lane & 15), TL * j + (lane >> 4) + 4 * e);
+    for (int e = 0; e < 4; ++e) er[e] = elem_ref(a.ns, TL * r + (lane & 15), TL * j + (lane >> 4) + 4 * e);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         v[e] = er[e].idx >= 0 ? a.payload[er[e].idx] : er[e].pad;
@@ -454,6 +493,85 @@ __device__ __forceinline__ int p_uses(int p, int r) {
     return u;
 }
 
+// ------------------------------------------------- the 16-pivot tile factor
+// Every 16-lane row of the wave holds the rows of the diagonal tile (r[j] =
+// element (li, j)) and one row of the panel (p[j]); pivot k scales column k
+// by 1/L_kk and subtracts L_jk (lane j's r[k], DPP row_newbcast) times it
+// from columns j > k, with v_fmac_f64_dpp's neg modifier (no negated copies).
+// Unlike chol_factor16 (k_chol_col) the next pivot's 1/sqrt is started as
+// soon as its column is updated and its four dependent operations (v_rsq_f64
+// and one Newton step, ~1 ulp) are interleaved with the remaining updates of
+// the current pivot, so the chain's latency hides under their issue.  Every
+// instruction is inline asm in program order; s_nop 1 gives a DPP read of a
+// just-written VGPR its two wait states.
+template <int J>
+__device__ __forceinline__ void gj_upd2(double &rj, double &pj, double rk, double pk) {
+    asm volatile("v_fmac_f64_dpp %0, %2, -%2 row_newbcast:%4 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_fmac_f64_dpp %1, %2, -%3 row_newbcast:%4 row_mask:0xf bank_mask:0xf"
+                 : "+v"(rj), "+v"(pj) : "v"(rk), "v"(pk), "n"(J));
+}
+struct NewtonState {
+    double d, h, g0, a, b, c15;
+};
+template <int STEP>
+__device__ __forceinline__ void gj_newton(NewtonState &n) {  // g1 = g0 (1.5 - (d/2) g0^2)
+    if constexpr (STEP == 0) asm volatile("v_mul_f64 %0, %1, %2" : "=v"(n.a) : "v"(n.h), "v"(n.g0));
+    if constexpr (STEP == 1) asm volatile("v_fma_f64 %0, -%1, %2, %3" : "=v"(n.b) : "v"(n.a), "v"(n.g0), "v"(n.c15));
+    if constexpr (STEP == 2) asm volatile("v_mul_f64 %0, %1, %2" : "=v"(n.g0) : "v"(n.g0), "v"(n.b));
+}
+// updates of columns K+2+U.. of pivot K, the Newton steps after updates 1, 3, 5
+template <int K, int U>
+__device__ __forceinline__ void gj_rest(double (&r)[16], double (&p)[16], NewtonState &n) {
+    if constexpr (K + 2 + U <= 15) {
+        gj_upd2<K + 2 + U>(r[K + 2 + U], p[K + 2 + U], r[K], p[K]);
+        if constexpr (U == 1) gj_newton<0>(n);
+        if constexpr (U == 3) gj_newton<1>(n);
+        if constexpr (U == 5) gj_newton<2>(n);
+        gj_rest<K, U + 1>(r, p, n);
+    } else {  // fewer updates than Newton steps: the rest back to back
+        if constexpr (U <= 1) gj_newton<0>(n);
+        if constexpr (U <= 3) gj_newton<1>(n);
+        if constexpr (U <= 5) gj_newton<2>(n);
+    }
+}
+template <int K>
+__device__ __forceinline__ void gj_step(double (&r)[16], double (&p)[16], double (&dinv)[16], NewtonState &n,
+                                        bool &nonpos) {
+    const double g = n.g0;
+    asm volatile("v_mul_f64 %0, %0, %2\n\tv_mul_f64 %1, %1, %2" : "+v"(r[K]), "+v"(p[K]) : "v"(g));
+    dinv[K] = g;
+    if constexpr (K < 15) {
+        asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %2, -%2 row_newbcast:%4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_fmac_f64_dpp %1, %2, -%3 row_newbcast:%4 row_mask:0xf bank_mask:0xf"
+                     : "+v"(r[K + 1]), "+v"(p[K + 1]) : "v"(r[K]), "v"(p[K]), "n"(K + 1));
+        asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf"
+                     : "=v"(n.d) : "v"(r[K + 1]), "n"(K + 1));
+        asm volatile("v_rsq_f64 %0, %1" : "=v"(n.g0) : "v"(n.d));
+        asm volatile("v_mul_f64 %0, %1, 0.5" : "=v"(n.h) : "v"(n.d));
+        nonpos |= !(n.d > 0.0);
+        gj_rest<K, 0>(r, p, n);
+    }
+}
+template <int... K>
+__device__ __forceinline__ void gj_steps(double (&r)[16], double (&p)[16], double (&dinv)[16], NewtonState &n,
+                                         bool &nonpos, std::integer_sequence<int, K...>) {
+    (gj_step<K>(r, p, dinv, n, nonpos), ...);
+}
+__device__ __forceinline__ void gj_factor16(double (&r)[16], double (&p)[16], double (&dinv)[16], int lane,
+                                            int *bad) {
+    NewtonState n;
+    n.c15 = 1.5;
+    asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "=v"(n.d) : "v"(r[0]));
+    asm volatile("v_rsq_f64 %0, %1" : "=v"(n.g0) : "v"(n.d));
+    asm volatile("v_mul_f64 %0, %1, 0.5" : "=v"(n.h) : "v"(n.d));
+    bool nonpos = !(n.d > 0.0);
+    gj_newton<0>(n);
+    gj_newton<1>(n);
+    gj_newton<2>(n);
+    gj_steps(r, p, dinv, n, nonpos, std::make_integer_sequence<int, 16>{});
+    if (lane == 0 && nonpos) *bad = 1;
+}
+
 // ------------------------------------------------------------------- W0
 // The pivot: the chain on the diagonal tile with the b row (lane 0) and the
 // identity (lanes 16..31) as panel rows -> L_r (rows), y_r, L_r^-T rows.
@@ -470,7 +588,7 @@ __device__ __forceinline__ void pivot(const Args &a, const Rs &rs, Smem &S, int 
 #pragma unroll
     for (int j = 0; j < 16; ++j) pw[j] = grp == 0 ? (lane == 0 ? S.bv[j] : 0.0) : (grp == 1 && j == li ? 1.0 : 0.0);
     stamp(a, r, DBG_CHAIN0);
-    gj::gj_factor16(rw, pw, dinv, lane, a.bad);
+    gj_factor16(rw, pw, dinv, lane, a.bad);
     stamp(a, r, DBG_CHAIN1);
     if (grp == 1)
 #pragma unroll
@@ -720,6 +838,59 @@ __device__ __forceinline__ bool u_loop(const Args &a, const Rs &rs, Smem &S, int
     return true;
 }
 
+// trial cameras and the camera part of the model decrease from dc (LDS),
+// as camera_trial (k_chol_backsolve's epilogue) with the system read from
+// its source; red: 3 x NTH / 64 doubles
+// (scalar arguments: a reference to the kernel's Args would put a copy of it
+// on the stack of every lane)
+template <int NTH>
+__device__ __attribute__((noinline)) void cam_trial(int nc, const double *Rt, double *Rt_new, double *cam_out,
+                                                    double lambda, const double *payload, int32_t ns,
+                                                    const double *dc, double *red, const double *camlin = nullptr) {
+    // diag U and g_c: the payload's vectors, or (finish folded into the solve) the camera blocks themselves
+    const double *du = payload + pay_vec_base(ns), *gc = du + ns;
+    double m = 0, dn = 0, xn = 0;
+    constexpr int NWT = NTH / 64;
+    for (int c = threadIdx.x; c < nc; c += NTH) {
+        const double *d = dc + 6 * c;
+        double dR[9];
+        rotvec_to_R(d[0], d[1], d[2], dR);
+        const double *R = Rt + 12 * c;
+        double *Rn = Rt_new + 12 * c;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Rn[3 * i + j] = dR[3 * i] * R[j] + dR[3 * i + 1] * R[3 + j] + dR[3 * i + 2] * R[6 + j];
+        for (int i = 0; i < 3; ++i) {
+            Rn[9 + i] = R[9 + i] + d[3 + i];
+            xn += R[9 + i] * R[9 + i];
+        }
+        for (int i = 0; i < 6; ++i) {
+            const double u = camlin ? cam_u(camlin, c, i, i) : du[6 * c + i];
+            const double g = camlin ? camlin[CAMLIN * c + 21 + i] : gc[6 * c + i];
+            m += d[i] * (lambda * clampd(u) * d[i] - g);
+            dn += d[i] * d[i];
+        }
+    }
+    // fixed order: a butterfly inside each wave, then the NW wave sums in
+    // wave order (a serial sum over all THREADS values was a ~THREADS-long
+    // dependent chain of LDS loads and adds on the solve's tail)
+    double v[3] = {m, dn, xn};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) red[k * NWT + w] = v[k];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double s = 0.0;
+#pragma unroll
+        for (int t = 0; t < NWT; ++t) s += red[threadIdx.x * NWT + t];
+        cam_out[threadIdx.x] = s;
+    }
+}
+
 template <int TR, int TLS>
 __global__ void __launch_bounds__(THREADS) k_gjr_solve(Args a) {
     if (a.gate && !*a.gate) return;  // device-side LM control: iteration gated off
@@ -763,7 +934,7 @@ __global__ void __launch_bounds__(THREADS) k_gjr_solve(Args a) {
     for (int i = threadIdx.x; i < 6 * a.ct.nc; i += THREADS)
         dc[i] = __hip_atomic_load(a.x + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    gj::cam_trial<THREADS>(a.ct.nc, a.ct.Rt, a.ct.Rt_new, a.ct.cam_out, *a.lam, a.payload, a.ns, dc, red,
+    cam_trial<THREADS>(a.ct.nc, a.ct.Rt, a.ct.Rt_new, a.ct.cam_out, *a.lam, a.payload, a.ns, dc, red,
                            a.src.slab ? a.src.camlin : nullptr);
 }
 

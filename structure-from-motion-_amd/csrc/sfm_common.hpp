@@ -94,12 +94,10 @@ struct ThreadCtx {
     hipEvent_t ev[8] = {};
     DevBuf buf[12];
     HostBuf pinned;
-    void *gj_ints = nullptr;  // sfm_reduced_solve: the flag buffer its epochs refer to
-    int gj_epoch = 0;
-    int gj_nT = 0, gj_nseg = 0;  // ... and the layout they were carved with
-    void *gjr_words = nullptr;   // ... the row-distributed solve's granule records (buf[7])
+    void *gjr_words = nullptr;   // sfm_reduced_solve: the granule records its tags refer to (buf[7]; no
+                                 // other entry point touches buf[7] or buf[8], the tags live across calls)
     unsigned gjr_tag = 0;
-    int gjr_nT = 0;
+    int gjr_nT = 0;              // ... and the layout they were carved with
     void *nl_sync = nullptr;     // sfm_nonlinear_pnp's cross-workgroup sums (zeroed once; epoch-tagged flags)
     unsigned nl_epoch = 0;
     int nl_resident = -1;        // sfm_nonlinear_pnp: workgroups resident at once (computed on first use)

@@ -21,8 +21,8 @@ import test_ba_step as S
 
 pytestmark = pytest.mark.gpu
 FACTOR = 16.0
-VARIANTS = [("SFM_SOLVE", "gj"), ("SFM_SOLVE", "gjseg"), ("SFM_SOLVE", "chol"), ("SFM_PLAN_HOST", "0"),
-            ("SFM_PLAN_HOST", "1"), ("SFM_SWEEP_RANGES", "1"), ("SFM_SWEEP_RANGES", "8")]
+VARIANTS = [("SFM_SOLVE", "gj"), ("SFM_SOLVE", "chol"), ("SFM_PLAN_HOST", "0"), ("SFM_PLAN_HOST", "1"),
+            ("SFM_SWEEP_RANGES", "1"), ("SFM_SWEEP_RANGES", "8")]
 VARIANTS += [(e, v) for e in ("SFM_LINEARIZE_CAM_LDS", "SFM_BACKSUB_CAM_LDS", "SFM_CAMLIN_FUSED", "SFM_FINISH_FUSED",
                               "SFM_GJR_FOLD") for v in ("0", "1")]
 

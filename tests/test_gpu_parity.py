@@ -996,17 +996,15 @@ def _spd(n, seed, cond=1e4):
     return 0.5 * (S + S.T), rng.standard_normal(n)
 
 
-@pytest.mark.parametrize("solver", ["gj", "gjseg", "chol"])
+@pytest.mark.parametrize("solver", ["gj", "chol"])
 @pytest.mark.parametrize("n", [1, 6, 16, 17, 48, 150, 300, 304, 600, 1200, 1800, 2100])
 def test_reduced_solve(core, monkeypatch, n, solver):
     """The reduced-camera solvers against LAPACK on SPD systems with condition
-    number 1e4: the row-distributed persistent block Gauss-Jordan solve
-    (default; gjr_solve.hpp, up to 128 tile rows -- n = 2100 falls back to
-    the tiled Cholesky), the column-block segment Gauss-Jordan solve
-    (SFM_SOLVE=gjseg, gj_solve.hpp: the live fallback when the row layout
-    declines) and the tiled Cholesky (SFM_SOLVE=chol: k_chol_col launches,
+    number 1e4: the persistent block Gauss-Jordan solve (default;
+    gjr_solve.hpp, up to 128 tile rows -- n = 2100 falls back to the tiled
+    Cholesky) and the tiled Cholesky (SFM_SOLVE=chol: k_chol_col launches,
     forward substitution folded in, back substitution).  Relative error
-    <= 1e-11 (all backward stable; kappa * eps ~ 2e-12); deterministic."""
+    <= 1e-11 (both backward stable; kappa * eps ~ 2e-12); deterministic."""
     monkeypatch.setenv("SFM_SOLVE", solver)
     S, b = _spd(n, seed=n)
     x_ref = np.linalg.solve(S, b)
@@ -1015,7 +1013,7 @@ def test_reduced_solve(core, monkeypatch, n, solver):
     assert np.array_equal(x, core.reduced_solve(S, b))
 
 
-@pytest.mark.parametrize("solver", ["gj", "gjseg", "chol"])
+@pytest.mark.parametrize("solver", ["gj", "chol"])
 @pytest.mark.parametrize("n", [40, 300, 1200])
 def test_reduced_solve_not_spd(core, monkeypatch, n, solver):
     """A non-positive pivot is reported by either solver."""
