@@ -1385,6 +1385,58 @@ def select_pairs(word, img_start, n_words, top_k=20):
     return dict(neighbour=neighbour, score=score, dot=dot, norm2=norm2, df=df)
 
 
+def _register(name, k, min_n, slots, K, X, view_start, pt_idx, xy, samples, threshold, min_inliers, refit_rounds,
+              max_nfev, want_counts, want_models):
+    """register_views (k = 6, slots = 1) and register_views_p3p (k = 3, slots
+    = 4): the coercions, the checks before a device is looked for, the call and
+    the output tuple.  ``slots`` > 1 brings the n_sol table and a slot axis."""
+    K = _f64(K).reshape(3, 3)
+    X = _f64(X).reshape(-1, 3)
+    vs = np.ascontiguousarray(view_start, dtype=np.int64).reshape(-1)
+    pt = np.ascontiguousarray(pt_idx, dtype=np.int32).reshape(-1)
+    xy = _f64(xy).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    if len(vs) < 1 or len(xy) != len(pt):
+        raise ValueError(f"{name}: view_start needs V + 1 entries and pt_idx, xy one row per correspondence")
+    V = len(vs) - 1
+    if samples.ndim != 3 or samples.shape[0] != V or samples.shape[2] != k or samples.shape[1] < 1:
+        raise ValueError(f"{name}: samples must be (V, H, {k}) with H >= 1")
+    H = samples.shape[1]
+    threshold = float(threshold)
+    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < min_n or int(refit_rounds) < 0
+           or int(max_nfev) <= 0 or H > 1 << 20 or not _csr_ok(vs, pt, len(X)))
+    if not bad:
+        n_v = np.diff(vs)
+        live = n_v >= min_n
+        if live.any():
+            s = samples[live]
+            srt = np.sort(s, axis=2)
+            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_v[live]).any()
+                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
+            if not bad:
+                require_device()
+    multi = slots > 1
+    per = (H, slots) if multi else (H,)
+    C, R, cost = np.zeros((V, 3)), np.zeros((V, 9)), np.zeros(V)
+    n_inl, hyp, count, info = (np.zeros(V, dtype=np.int32) for _ in range(4))
+    inlier = np.zeros(len(pt), dtype=np.uint8)
+    n_sol = np.zeros((V, H), dtype=np.int32) if want_counts and multi else None
+    counts = np.zeros((V,) + per, dtype=np.int32) if want_counts else None
+    models = np.zeros((V,) + per + (12,)) if want_models else None
+    tables = [(n_sol, _i32)] * multi + [(counts, _i32), (models, _d)]  # the optional arrays, in the C order
+    tables = [None if a is None else _p(a, t) for a, t in tables]
+    _check(getattr(_lib, "sfm_" + name)(
+        _p(K), _p(X), len(X), _p(vs, _i64), V, _p(pt, _i32), _p(xy), len(pt), _p(samples, _i32), H, threshold,
+        int(min_inliers), int(refit_rounds), int(max_nfev), _p(C), _p(R), _p(cost), _p(n_inl, _i32), _p(hyp, _i32),
+        _p(count, _i32), _p(info, _i32), _p(inlier, _u8), *tables, DEVICE))
+    out = (C, R.reshape(V, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info)
+    if want_counts:
+        out += (n_sol, counts) if multi else (counts,)
+    if want_models:
+        out += (models.reshape((V,) + per + (3, 4)),)
+    return out
+
+
 def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=6, refit_rounds=3, max_nfev=50,
                    want_counts=False, want_models=False):
     """Batched view registration (sfm_register_views): for every view, 6-point
@@ -1401,47 +1453,8 @@ def register_views(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inl
     counts (V, H) int32 with want_counts and models (V, H, 3, 4) with
     want_models.  The arguments are checked before a device is looked for;
     V = 0, or no view of six correspondences, returns without one."""
-    K = _f64(K).reshape(3, 3)
-    X = _f64(X).reshape(-1, 3)
-    vs = np.ascontiguousarray(view_start, dtype=np.int64).reshape(-1)
-    pt = np.ascontiguousarray(pt_idx, dtype=np.int32).reshape(-1)
-    xy = _f64(xy).reshape(-1, 2)
-    samples = np.ascontiguousarray(samples, dtype=np.int32)
-    if len(vs) < 1 or len(xy) != len(pt):
-        raise ValueError("register_views: view_start needs V + 1 entries and pt_idx, xy one row per correspondence")
-    V = len(vs) - 1
-    if samples.ndim != 3 or samples.shape[0] != V or samples.shape[2] != 6 or samples.shape[1] < 1:
-        raise ValueError("register_views: samples must be (V, H, 6) with H >= 1")
-    H = samples.shape[1]
-    threshold = float(threshold)
-    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 6 or int(refit_rounds) < 0
-           or int(max_nfev) <= 0 or not _csr_ok(vs, pt, len(X)))
-    if not bad:
-        n_v = np.diff(vs)
-        live = n_v >= 6
-        if live.any():
-            s = samples[live]
-            srt = np.sort(s, axis=2)
-            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_v[live]).any()
-                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
-            if not bad:
-                require_device()
-    C, R, cost = np.zeros((V, 3)), np.zeros((V, 9)), np.zeros(V)
-    n_inl, hyp, count, info = (np.zeros(V, dtype=np.int32) for _ in range(4))
-    inlier = np.zeros(len(pt), dtype=np.uint8)
-    counts = np.zeros((V, H), dtype=np.int32) if want_counts else None
-    models = np.zeros((V, H, 12)) if want_models else None
-    _check(_lib.sfm_register_views(
-        _p(K), _p(X), len(X), _p(vs, _i64), V, _p(pt, _i32), _p(xy), len(pt), _p(samples, _i32), H, threshold,
-        int(min_inliers), int(refit_rounds), int(max_nfev), _p(C), _p(R), _p(cost), _p(n_inl, _i32), _p(hyp, _i32),
-        _p(count, _i32), _p(info, _i32), _p(inlier, _u8), _p(counts, _i32) if want_counts else None,
-        _p(models) if want_models else None, DEVICE))
-    out = (C, R.reshape(V, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info)
-    if want_counts:
-        out += (counts,)
-    if want_models:
-        out += (models.reshape(V, H, 3, 4),)
-    return out
+    return _register("register_views", 6, 6, 1, K, X, view_start, pt_idx, xy, samples, threshold, min_inliers,
+                     refit_rounds, max_nfev, want_counts, want_models)
 
 
 def register_views_p3p(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min_inliers=4, refit_rounds=3,
@@ -1458,49 +1471,8 @@ def register_views_p3p(K, X, view_start, pt_idx, xy, samples, threshold=4.0, min
     4, 3, 4) with want_models, zero past n_sol.  The arguments are checked
     before a device is looked for; V = 0, or no view of four correspondences,
     returns without one."""
-    K = _f64(K).reshape(3, 3)
-    X = _f64(X).reshape(-1, 3)
-    vs = np.ascontiguousarray(view_start, dtype=np.int64).reshape(-1)
-    pt = np.ascontiguousarray(pt_idx, dtype=np.int32).reshape(-1)
-    xy = _f64(xy).reshape(-1, 2)
-    samples = np.ascontiguousarray(samples, dtype=np.int32)
-    if len(vs) < 1 or len(xy) != len(pt):
-        raise ValueError("register_views_p3p: view_start needs V + 1 entries and pt_idx, xy one row per "
-                         "correspondence")
-    V = len(vs) - 1
-    if samples.ndim != 3 or samples.shape[0] != V or samples.shape[2] != 3 or samples.shape[1] < 1:
-        raise ValueError("register_views_p3p: samples must be (V, H, 3) with H >= 1")
-    H = samples.shape[1]
-    threshold = float(threshold)
-    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 4 or int(refit_rounds) < 0
-           or int(max_nfev) <= 0 or H > 1 << 20 or not _csr_ok(vs, pt, len(X)))
-    if not bad:
-        n_v = np.diff(vs)
-        live = n_v >= 4
-        if live.any():
-            s = samples[live]
-            srt = np.sort(s, axis=2)
-            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_v[live]).any()
-                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
-            if not bad:
-                require_device()
-    C, R, cost = np.zeros((V, 3)), np.zeros((V, 9)), np.zeros(V)
-    n_inl, hyp, count, info = (np.zeros(V, dtype=np.int32) for _ in range(4))
-    inlier = np.zeros(len(pt), dtype=np.uint8)
-    n_sol = np.zeros((V, H), dtype=np.int32) if want_counts else None
-    counts = np.zeros((V, H, 4), dtype=np.int32) if want_counts else None
-    models = np.zeros((V, H, 4, 12)) if want_models else None
-    _check(_lib.sfm_register_views_p3p(
-        _p(K), _p(X), len(X), _p(vs, _i64), V, _p(pt, _i32), _p(xy), len(pt), _p(samples, _i32), H, threshold,
-        int(min_inliers), int(refit_rounds), int(max_nfev), _p(C), _p(R), _p(cost), _p(n_inl, _i32), _p(hyp, _i32),
-        _p(count, _i32), _p(info, _i32), _p(inlier, _u8), _p(n_sol, _i32) if want_counts else None,
-        _p(counts, _i32) if want_counts else None, _p(models) if want_models else None, DEVICE))
-    out = (C, R.reshape(V, 3, 3), cost, n_inl, inlier.astype(bool), hyp, count, info)
-    if want_counts:
-        out += (n_sol, counts)
-    if want_models:
-        out += (models.reshape(V, H, 4, 3, 4),)
-    return out
+    return _register("register_views_p3p", 3, 4, 4, K, X, view_start, pt_idx, xy, samples, threshold, min_inliers,
+                     refit_rounds, max_nfev, want_counts, want_models)
 
 
 def reduced_solve(S, rhs):

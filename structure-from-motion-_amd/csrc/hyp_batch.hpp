@@ -134,7 +134,7 @@ __device__ __forceinline__ double wave_sum(double x) {
 // then the wave results as 0 + 1 or (0 + 1) + (2 + 3).  red: NW x NV.  The
 // butterfly is wave_sum's with the step as the outer loop -- NV independent
 // shuffles a step, not NV chains of six: with wave_sum per element the refits
-// that sum 29 values (k_reg_refine, k_p3p_refine) ran 2 % and 1 % slower.
+// that sum 29 values (k_rv_refine, register_refine.hpp) ran 2 % and 1 % slower.
 template <int NW, int NV> __device__ __forceinline__ void wg_sum(double (&x)[NV], double (*red)[NV]) {
     static_assert(NW == 2 || NW == 4, "the tree over the wave results is written out");
 #pragma unroll

@@ -17,19 +17,14 @@
 //                    the null vector, rv_post / pnp_projection finish the
 //                    model.  Score: a wave per hypothesis, the inlier rule over
 //                    tiles of 1024.
-//   k_reg_refine     one workgroup per view: winner (most inliers, then the
-//                    earliest), its mask, then rounds of Levenberg-Marquardt on
-//                    the 6 pose parameters over the current inliers, a re-score
-//                    of the whole view and the not-worse test.
+//   k_rv_refine<RvDlt6>  register_refine.hpp's: one workgroup per view, the
+//                    winner (most inliers, then the earliest hypothesis), its
+//                    mask and the refit from its pose.
 //
-// The inlier rule, the fixed-order sums and the refit are register_refine.hpp's,
-// shared with the calibrated 3-point entry point (register_p3p.hip).
-#include <cmath>
-#include <cstring>
-
-#include "hyp_batch.hpp"
+// The inlier rule, the score loop, that kernel and the host driver of a call
+// are register_refine.hpp's, shared with the calibrated 3-point entry point
+// (register_p3p.hip); what is here is the fit.
 #include "register_refine.hpp"
-#include "select.hpp"
 
 #pragma clang fp contract(off)
 
@@ -144,9 +139,9 @@ __device__ __forceinline__ void rv_post(const double (&p)[12], double (&C)[3], d
 __global__ void __launch_bounds__(RV_THREADS)
 k_reg_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_start,
                 const int32_t *__restrict__ pt_idx, const double2 *__restrict__ xy,
-                const int32_t *__restrict__ samples, int32_t H, Cam3 K, const int32_t *__restrict__ blk_start,
+                const int32_t *__restrict__ samples, int32_t H, Cam3 K, Cam3, const int32_t *__restrict__ blk_start,
                 const int32_t *__restrict__ tab, int32_t n_live, double thr, double *__restrict__ modelsP,
-                double *__restrict__ modelsCR, int32_t *__restrict__ counts) {
+                double *__restrict__ modelsCR, int32_t *__restrict__ counts, int32_t *) {
     __shared__ double sP[RV_HT][12];
     __shared__ double sX[RV_TILE * 3];
     __shared__ double2 sxy[RV_TILE];
@@ -207,97 +202,24 @@ k_reg_fit_score(const double *__restrict__ Xg, const int64_t *__restrict__ view_
     }
     __syncthreads();
 
-    // ---- score: a wave per hypothesis, the view's tile shared by all of them
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const double thr2 = thr * thr;
-    for_each_tile<RV_THREADS, RV_TILE>(
-        n, [&](int i, int c) { rv_stage(Xg, pt_idx, xy, vs + c, sX, sxy, i); },
-        [&](int nt) {
-            for (int hl = wave; hl < nh; hl += RV_WAVES) {
-                if (!sFin[hl]) continue;
-                double P[12];
-#pragma unroll
-                for (int j = 0; j < 12; ++j) P[j] = sP[hl][j];
-                const int cnt = wave_count(nt, [&](int i) {
-                    const double2 q = sxy[i];
-                    return rv_inlier(P, sX[3 * i], sX[3 * i + 1], sX[3 * i + 2], q.x, q.y, thr, thr2);
-                });
-                if (lane == 0) sCnt[hl] += cnt;  // this wave alone owns hl
-            }
-        });
+    // ---- score: a wave per finite hypothesis, the view's tile shared by all of them
+    rv_score(Xg, pt_idx, xy, vs, n, thr, nh, [&](int hl, int &m) { return sFin[m = hl] != 0; }, sP, sCnt, sX, sxy);
     if (tid < nh) counts[row0 + tid] = sFin[tid] ? sCnt[tid] : 0;
 }
 
-// One workgroup per view.  mask2: scratch of n_corr bytes.  Views of fewer
-// than six correspondences are the host's (info -1): nothing of them is read.
-__global__ void __launch_bounds__(RV_THREADS)
-k_reg_refine(const double *__restrict__ Xg, const int64_t *__restrict__ view_start,
-             const int32_t *__restrict__ pt_idx, const double2 *__restrict__ xy, int32_t H, Cam3 K, double thr,
-             int32_t min_inliers, int32_t refit_rounds, int32_t max_nfev, const double *__restrict__ modelsP,
-             const double *__restrict__ modelsCR, const int32_t *__restrict__ counts, uint8_t *mask2,
-             double *__restrict__ C_out, double *__restrict__ R_out, double *__restrict__ cost_out,
-             int32_t *__restrict__ n_inl_out, int32_t *__restrict__ hyp_out, int32_t *__restrict__ count_out,
-             int32_t *__restrict__ info_out, uint8_t *inlier) {
-    __shared__ int32_t sc[RV_WAVES];
-    __shared__ int64_t sh[RV_WAVES];
-    __shared__ int32_t sFirst;
-    __shared__ double red[RV_WAVES][RV_NV];
-    __shared__ double red2[RV_WAVES][2];
-    const int tid = threadIdx.x;
-    const int64_t v = blockIdx.x;
-    const int64_t vs = view_start[v];
-    const int n = (int)(view_start[v + 1] - vs);
-    if (n < 6) return;
-    const RvView w{Xg, pt_idx + vs, xy + vs, n};
-    uint8_t *mask = inlier + vs, *trial = mask2 + vs;
-    const double thr2 = thr * thr;
-
-    int32_t bc;
-    int64_t bh;
-    if (tid == 0) sFirst = H;
-    wg_select_best<RV_THREADS>(counts + v * H, H, sc, sh, bc, bh);  // holds a barrier
-    if (bh < 0) {  // every count is 0: the earliest finite hypothesis, if any
-        for (int32_t h = tid; h < H; h += RV_THREADS) {
-            const double *m = modelsP + (v * H + h) * 12, *mc = modelsCR + (v * H + h) * 12;
-            bool fin = true;
-            for (int j = 0; j < 12; ++j) fin = fin && isfinite(m[j]);
-            for (int j = 0; j < 3; ++j) fin = fin && isfinite(mc[j]);
-            if (fin) {
-                atomicMin(&sFirst, h);
-                break;
-            }
-        }
-        __syncthreads();
-        bh = sFirst < H ? sFirst : -1;
-        bc = 0;
+// k_rv_refine's policy: one model a hypothesis, the earliest of equal counts;
+// with every count 0, the earliest hypothesis whose P and C are finite.
+struct RvDlt6 {
+    static constexpr int SLOTS_PER_HYP = 1, MIN_N = 6;
+    static constexpr bool COST_TIE_BREAK = false;
+    static __device__ __forceinline__ bool usable(const double *modelsP, const double *modelsCR, const int32_t *, int64_t g) {
+        const double *m = modelsP + g * 12, *mc = modelsCR + g * 12;
+        bool fin = true;
+        for (int j = 0; j < 12; ++j) fin &= isfinite(m[j]);
+        for (int j = 0; j < 3; ++j) fin &= isfinite(mc[j]);
+        return fin;
     }
-    double C[3] = {0.0, 0.0, 0.0}, R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, cost = 0.0;
-    int info = -2, n_inl = 0;
-    if (bh < 0) {
-        for (int i = tid; i < n; i += RV_THREADS) mask[i] = 0;
-    } else {
-        double P[12];
-        const double *m = modelsP + (v * H + bh) * 12, *mc = modelsCR + (v * H + bh) * 12;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) P[j] = m[j];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) C[j] = mc[j];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) R[j] = mc[3 + j];
-        info = rv_refit(w, K, P, thr2, bc, min_inliers, refit_rounds, max_nfev, R, C, cost, n_inl, mask, trial, red,
-                        red2);
-    }
-    if (tid == 0) {
-        for (int j = 0; j < 3; ++j) C_out[3 * v + j] = C[j];
-        for (int j = 0; j < 9; ++j) R_out[9 * v + j] = R[j];
-        cost_out[v] = cost;
-        n_inl_out[v] = n_inl;
-        hyp_out[v] = (int32_t)bh;
-        count_out[v] = bh < 0 ? 0 : bc;
-        info_out[v] = info;
-    }
-}
+};
 
 }  // namespace sfm
 
@@ -309,95 +231,8 @@ extern "C" int sfm_register_views(const double *K, const double *X, int64_t n_pt
                                   int32_t refit_rounds, int32_t max_nfev, double *C, double *R, double *cost,
                                   int32_t *n_inliers, int32_t *best_hyp, int32_t *best_count, int32_t *info,
                                   uint8_t *inlier, int32_t *counts, double *models, int device) {
-    SFM_CHECK_ARG(V >= 0 && n_corr >= 0 && n_pts >= 0, "V < 0, n_corr < 0 or n_pts < 0");
-    SFM_CHECK_ARG(H >= 1 && H <= (int64_t)1 << 20, "H must lie in [1, 2^20]");
-    SFM_CHECK_ARG(std::isfinite(threshold) && threshold > 0.0, "threshold must be finite and positive");
-    SFM_CHECK_ARG(min_inliers >= 6, "min_inliers must be at least 6");
-    SFM_CHECK_ARG(refit_rounds >= 0, "refit_rounds < 0");
-    SFM_CHECK_ARG(max_nfev > 0, "max_nfev must be positive");
-    SFM_CHECK_ARG(V < (int64_t)0x7fffffff / H, "V x H too large for one call");
-    SFM_CHECK_ARG(view_start && K, "null pointer");
-    SFM_TRY(check_csr(view_start, V, n_corr, "view_start", "correspondence", 0x7fffffff,
-                      "a view has too many correspondences"));
-    const int64_t n_live = count_live(view_start, V, 6);
-    SFM_CHECK_ARG(n_corr == 0 || (pt_idx && xy && X), "null pointer");
-    SFM_TRY(check_index(pt_idx, n_corr, n_pts, "point index outside [0, n_pts)"));
-    SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    SFM_TRY(check_samples(view_start, V, samples, H, 6, 6, "sample outside [0, n_v)"));
-    if (V == 0) return 0;
-    SFM_CHECK_ARG(C && R && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
-                  "null pointer");
-    // info -1: fewer than six correspondences.  Also what the live views start from.
-    for (int64_t v = 0; v < V; ++v) {
-        if (view_start[v + 1] - view_start[v] >= 6) continue;
-        for (int j = 0; j < 3; ++j) C[3 * v + j] = 0.0;
-        for (int j = 0; j < 9; ++j) R[9 * v + j] = j % 4 == 0 ? 1.0 : 0.0;
-        cost[v] = 0.0;
-        n_inliers[v] = 0;
-        best_hyp[v] = -1;
-        best_count[v] = 0;
-        info[v] = -1;
-        for (int64_t k = view_start[v]; k < view_start[v + 1]; ++k) inlier[k] = 0;
-        if (counts) std::memset(counts + v * H, 0, (size_t)H * sizeof(int32_t));
-        if (models) std::memset(models + v * H * 12, 0, (size_t)H * 12 * sizeof(double));
-    }
-    if (n_live == 0) return 0;
-
-    ThreadCtx *c = thread_ctx(device);
-    if (!c) return SFM_ERR_HIP;
-    TileTable tt;
-    SFM_TRY(tt.build(c->pinned, n_live, view_start, V, 6, H, RV_HT, RV_TILE));
-
-    const size_t VH = (size_t)V * (size_t)H;
-    Pack in(c->buf[0]), out(c->buf[1]);
-    const auto i_vs = in.add<int64_t>(V + 1);
-    const auto i_xy = in.add<double2>(n_corr);
-    const auto i_X = in.add<double>(3 * n_pts);
-    const auto i_pt = in.add<int32_t>(n_corr), i_s = in.add<int32_t>(6 * VH);
-    const auto i_t = in.add<int32_t>(tt.words());  // the block table
-    const auto o_C = out.add<double>(3 * V), o_R = out.add<double>(9 * V), o_cost = out.add<double>(V);
-    const auto o_info = out.add<int32_t>(V), o_ninl = out.add<int32_t>(V);
-    const auto o_hyp = out.add<int32_t>(V), o_bc = out.add<int32_t>(V), o_cnt = out.add<int32_t>(VH);
-    const auto o_mP = out.add<double>(12 * VH), o_mCR = out.add<double>(12 * VH);
-    const auto o_mask = out.add<uint8_t>(n_corr), o_m2 = out.add<uint8_t>(n_corr);  // o_m2: the refits' trial mask
-    SFM_TRY(in.reserve());
-    SFM_TRY(out.reserve());
-    Cam3 cam;
-    std::memcpy(cam.k, K, sizeof cam.k);
-    hipStream_t s = c->stream;
-    CallTimer tm(c);
-    SFM_TRY(tm.mark(s));
-    SFM_TRY(in.upload(i_vs, view_start, s));
-    SFM_TRY(in.upload(i_xy, xy, s));
-    SFM_TRY(in.upload(i_X, X, s));
-    SFM_TRY(in.upload(i_pt, pt_idx, s));
-    SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, tt.blk, s));
-    SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_reg_fit_score, dim3((unsigned)tt.blocks), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
-                       in.ptr(i_pt), in.ptr(i_xy), in.ptr(i_s), (int32_t)H, cam, in.ptr(i_t),
-                       in.ptr(i_t, n_live + 1), (int32_t)n_live, threshold, out.ptr(o_mP), out.ptr(o_mCR),
-                       out.ptr(o_cnt));
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(tm.split(s));  // [3]: the fit-and-score kernel alone
-    hipLaunchKernelGGL(k_reg_refine, dim3((unsigned)V), dim3(RV_THREADS), 0, s, in.ptr(i_X), in.ptr(i_vs),
-                       in.ptr(i_pt), in.ptr(i_xy), (int32_t)H, cam, threshold, min_inliers, refit_rounds, max_nfev,
-                       out.ptr(o_mP), out.ptr(o_mCR), out.ptr(o_cnt), out.ptr(o_m2), out.ptr(o_C), out.ptr(o_R),
-                       out.ptr(o_cost), out.ptr(o_ninl), out.ptr(o_hyp), out.ptr(o_bc), out.ptr(o_info),
-                       out.ptr(o_mask));
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(tm.mark(s));
-    SFM_TRY(for_each_live_run(view_start, V, 6, [&](int64_t v0, int64_t v1, int64_t k0, int64_t k1) -> int {
-        SFM_TRY(out.download_rows(C, o_C, 3, v0, v1, s));
-        SFM_TRY(out.download_rows(R, o_R, 9, v0, v1, s));
-        SFM_TRY(out.download_rows(cost, o_cost, 1, v0, v1, s));
-        SFM_TRY(out.download_rows(info, o_info, 1, v0, v1, s));
-        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, v0, v1, s));
-        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, v0, v1, s));
-        SFM_TRY(out.download_rows(best_count, o_bc, 1, v0, v1, s));
-        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
-        SFM_TRY(out.download_rows(counts, o_cnt, H, v0, v1, s));
-        return out.download_rows(models, o_mP, 12 * H, v0, v1, s);
-    }));
-    return tm.finish(s);
+    static const RvSpec spec{6, 6, 1, RV_HT, false, k_reg_fit_score, k_rv_refine<RvDlt6>,
+                             "min_inliers must be at least 6", "V x H too large for one call"};
+    return rv_run(spec, K, X, n_pts, view_start, V, pt_idx, xy, n_corr, samples, H, threshold, min_inliers, refit_rounds,
+                  max_nfev, C, R, cost, n_inliers, best_hyp, best_count, info, inlier, nullptr, counts, models, device);
 }

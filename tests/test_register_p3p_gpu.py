@@ -253,6 +253,65 @@ def test_degenerate_samples_have_no_solution_and_change_nothing_else(core, scene
     assert np.array_equal(other[10][2:], base[10][2:])
 
 
+def small_batch(core, sc):
+    """Three views cut from the scene, for the shared branches below: view 2's
+    five correspondences, the degenerate view's 40 (inside one tile) and view
+    7's 1,025 followed by view 2's five, which are outliers to it (1,030: past
+    the tile edge at 1,024).  Returns (view_start, pt_idx, xy, samples): the
+    table at H = 5, the degenerate view's first two samples degenerate as in
+    sample_table."""
+    vs, d = sc["view_start"], p3.DEGENERATE
+    sel = np.concatenate([np.arange(vs[2], vs[3]), np.arange(vs[d], vs[d + 1]), np.arange(vs[7], vs[8]),
+                          np.arange(vs[2], vs[3])])
+    start = np.array([0, 5, 45, 1075])
+    t = core.p3p_samples(np.diff(start), 5, p3.SAMPLE_SEED)
+    t[1, 0], t[1, 1] = (0, 1, 2), (3, 4, 5)
+    return start, sc["pt_idx"][sel], sc["xy"][sel], t
+
+
+def test_every_count_zero_returns_the_earliest_solution(core, scene):
+    """threshold 1e-200: its square underflows to 0 and no squared error is
+    below 0, so every count of every view is 0.  The winner is then slot 0 of
+    the first hypothesis with a solution, returned unrefitted (info -3) with an
+    empty mask; C, R are that model's pose, to the 1e-9 of
+    test_too_few_inliers_returns_the_winning_solution."""
+    vs, pt, xy, t = small_batch(core, scene)
+    C, R, cost, n_inl, inl, hyp, count, info, n_sol, counts, models = core.register_views_p3p(
+        K, scene["X"], vs, pt, xy, t, threshold=1e-200, want_counts=True, want_models=True)
+    assert not counts.any() and not count.any() and not n_inl.any() and not inl.any() and not cost.any()
+    assert not n_sol[1, :2].any()
+    for v in range(3):
+        assert info[v] == -3 and n_sol[v].any() and hyp[v] == np.argmax(n_sol[v] > 0), (v, info[v], hyp[v], n_sol[v])
+        Rk, Ck = pose_of(models[v, hyp[v], 0])
+        print(f"view {v}: best_hyp {hyp[v]} |dC| {np.abs(C[v] - Ck).max():.3g} |dR| {np.abs(R[v] - Rk).max():.3g}")
+        assert np.allclose(C[v], Ck, rtol=0, atol=1e-9) and np.allclose(R[v], Rk, rtol=0, atol=1e-9)
+
+
+def test_a_view_without_a_usable_hypothesis_is_refused_and_changes_nothing_else(core, scene):
+    """every sample of one view degenerate (three collinear points, or one 3-D
+    point under two indices): no solution, no winner (info -2), and the other
+    views' outputs bit for bit those of the call with the ordinary table"""
+    vs, pt, xy, t = small_batch(core, scene)
+    bad = t.copy()
+    bad[1] = [(0, 1, 2), (3, 4, 5), (2, 0, 1), (4, 3, 6), (3, 4, 7)]
+    n_v = np.diff(vs)
+
+    def call(tab):
+        out = core.register_views_p3p(K, scene["X"], vs, pt, xy, tab, threshold=THR, want_counts=True,
+                                      want_models=True)
+        C, R, cost, n_inl, inl, hyp, count, info, n_sol, counts, models = out
+        return [(C[v], R[v], cost[v], n_inl[v], inl[vs[v]:vs[v + 1]], hyp[v], count[v], info[v], n_sol[v], counts[v],
+                 models[v]) for v in range(3)]
+    base, out = call(t), call(bad)
+    C, R, cost, n_inl, inl, hyp, count, info, n_sol, counts, models = out[1]
+    assert not n_sol.any() and not counts.any() and not models.any()
+    assert hyp == -1 and info == -2 and count == 0 and n_inl == 0 and cost == 0
+    assert np.array_equal(R, np.eye(3)) and not C.any() and len(inl) == n_v[1] and not inl.any()
+    assert base[1][7] != -2  # the ordinary table has solutions for this view
+    for v in (0, 2):
+        assert same(out[v], base[v]), v
+
+
 def test_small_views(scene, results):
     for H in p3.HS:
         C, R, cost, n_inl, inl, hyp, count, info, n_sol, counts, models = results[H]

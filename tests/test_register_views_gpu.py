@@ -190,6 +190,38 @@ def test_too_few_inliers_returns_the_winning_hypothesis(core, scene, results, go
     assert np.allclose(C, Cn, rtol=0, atol=1e-9) and np.allclose(R, Rn, rtol=0, atol=1e-9) and len(set(s)) == 6
 
 
+def small_batch(sc):
+    """Three views cut from the scene, for the shared branches below: view 0's
+    five correspondences (below the minimum: dead), the first 40 of view 4
+    (inside one tile) and view 7's 1,025 followed by view 0's five, which are
+    outliers to it (1,030: past the tile edge at 1,024).  Returns (view_start,
+    pt_idx, xy)."""
+    vs = sc["view_start"]
+    sel = np.concatenate([np.arange(vs[0], vs[1]), np.arange(vs[4], vs[4] + 40), np.arange(vs[7], vs[8]),
+                          np.arange(vs[0], vs[1])])
+    return np.array([0, 5, 45, 1075]), sc["pt_idx"][sel], sc["xy"][sel]
+
+
+def test_every_count_zero_returns_the_earliest_finite_hypothesis(core, scene):
+    """threshold 1e-200: its square underflows to 0 and no squared error is
+    below 0, so every count of every view is 0.  The winner is then the first
+    hypothesis whose model is finite, returned unrefitted (info -3) with an
+    empty mask; C, R are that hypothesis's own pose (pose_from_null of its
+    model, to the 1e-9 of test_too_few_inliers_returns_the_winning_hypothesis)."""
+    vs, pt, xy = small_batch(scene)
+    t = core.register_samples(np.diff(vs), 5, rv.SAMPLE_SEED)
+    C, R, cost, n_inl, inl, hyp, count, info, counts, models = core.register_views(
+        K, scene["X"], vs, pt, xy, t, threshold=1e-200, want_counts=True, want_models=True)
+    assert not counts.any() and not count.any() and not n_inl.any() and not inl.any() and not cost.any()
+    assert info[0] == -1 and hyp[0] == -1 and not C[0].any() and np.array_equal(R[0], np.eye(3))
+    for v in (1, 2):
+        finite = np.isfinite(models[v]).all(axis=(1, 2))
+        assert info[v] == -3 and finite.any() and hyp[v] == np.argmax(finite), (v, info[v], hyp[v], finite)
+        Cn, Rn, _ = rv.pose_from_null((np.linalg.inv(K) @ models[v, hyp[v]]).reshape(12))
+        print(f"view {v}: best_hyp {hyp[v]} |dC| {np.abs(C[v] - Cn).max():.3g} |dR| {np.abs(R[v] - Rn).max():.3g}")
+        assert np.allclose(C[v], Cn, rtol=0, atol=1e-9) and np.allclose(R[v], Rn, rtol=0, atol=1e-9)
+
+
 def test_store_round_trip(core):
     """sfm_multiview.register_views on a small synthetic store: three candidate
     images, the middle one with 30 % wrong observations"""
