@@ -638,6 +638,100 @@ int sfm_init_pairs(const double *K, const int64_t *pair_start, int64_t P, const 
                    uint8_t *good, double *angle, double *cands, int32_t *hcounts, double *hmodels, int device);
 
 /* ---------------------------------------------------------------------
+ * Global rotation averaging: the rotation of every camera from the relative
+ * rotations of the pairs, in one call -- one spanning tree, consensus sweeps
+ * that repair it, a weighted refit on the consensus set.  sfm_init_pairs gives
+ * a relative pose for every verified pair and the incremental chain uses one of
+ * them; this uses all of them, and its edge mask is the loop-consistency check
+ * on pairs that passed RANSAC with a wrong geometry.  The reference has no
+ * counterpart.
+ * n_images = N >= 0 cameras; the n_edges = E >= 0 edges are pair_ij (E x 2
+ * int32: i != j, both in [0, N); duplicate pairs and both orientations of a
+ * pair are allowed, each is an edge of its own) with R_rel (E x 3 x 3 fp64,
+ * row-major) under R_j ~ R_rel R_i for x_cam = R (X - C): sfm_init_pairs' R of
+ * the pair (i, j), whose camera i is [I | 0].  R_rel must hold rotations:
+ * finiteness is checked, orthogonality is not.  weight (E, finite and > 0) is
+ * nullable: every weight 1.  threshold, the inlier angle in radians, finite, in
+ * (0, pi); consensus_sweeps >= 0; max_sweeps >= 0; tol >= 0 radians; E <= 2^30.
+ * A violation is SFM_ERR_ARG, found on the host before a device is looked for,
+ * with nothing written.
+ * Definitions, from which every output follows; fp64 with no contraction:
+ *   products: (A B)[r][c] = (A[r][0] B[0][c] + A[r][1] B[1][c]) + A[r][2] B[2][c];
+ *     with A^T or B^T the same three terms in the same order, the transposed
+ *     factor read through swapped indices;
+ *   adjacency: node n's entries are the edges that contain n, by ascending edge
+ *     index e.  For e = (i, j): the entry (e, j, fwd) in i's list predicts
+ *     R_i = R_rel^T R_j, the entry (e, i, rev) in j's list predicts
+ *     R_j = R_rel R_i; P_a is the prediction of a node's entry a = 0 .. d - 1
+ *     from the neighbour's current rotation;
+ *   trace test of a prediction P against a matrix Q (another prediction or a
+ *     rotation): with both row-major as p[0..8], q[0..8],
+ *     t = (..((p0 q0 + p1 q1) + p2 q2) + ..) + p8 q8 -- the nine products of
+ *     tr(P Q^T) added left to right -- and the test is t >= tau with
+ *     tau = 1 + 2 cos(threshold), two fp64 operations on the C library's cos:
+ *     the angle between P and Q is at most threshold;
+ *   priority(seed, e), 64-bit unsigned arithmetic modulo 2^64:
+ *     z = seed + (e + 1) 0x9E3779B97F4A7C15;
+ *     z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9;
+ *     z = (z ^ (z >> 27)) 0x94D049BB133111EB;  priority = z ^ (z >> 31);
+ *   components and roots (host, union-find): each connected component of the
+ *     graph of all edges has one root, its node of highest degree, the lowest
+ *     index on ties; a node without edges is its own root.
+ * Stage 1, spanning tree (device, level-synchronous breadth-first search from
+ * all roots at once, as many levels as the graph is deep): a root has level 0
+ * and R = I.  A node not yet reached with an entry whose neighbour has level l
+ * gets level l + 1 and the prediction of the one such entry of smallest
+ * (priority(seed, e), e).
+ * Stage 2, consensus_sweeps Jacobi sweeps (every node reads the rotations of
+ * the sweep before): for a node that is not a root,
+ * support_a = #{ b : P_a passes the trace test against P_b } (b = a included),
+ * and R becomes P_a for the a of greatest support, the lowest a on ties.  d^2
+ * tests per node and sweep: the hot path.  One workgroup per node, of 64
+ * threads (one wave) up to degree 64, 128 up to 128 and 256 above; thread a
+ * keeps P_a in registers, the P_b pass through LDS in tiles of the workgroup's
+ * size as 72-byte records, and a node of more entries than threads walks the
+ * (a, b) tiles, forming each tile's predictions again from global memory.
+ * Stage 3, refit: Jacobi sweeps over the nodes that are not roots.  For the
+ * entries, in their order, whose P passes the trace test against the node's R
+ * (t its sum): M = P R^T, v = ((M21 - M12) / 2, (M02 - M20) / 2, (M10 - M01) / 2),
+ * s = sqrt((v0 v0 + v1 v1) + v2 v2), theta = atan2(s, (t - 1) / 2),
+ * log = v (theta / s) (v where s = 0); num += w_e log per component and
+ * den += w_e, left to right from 0; omega = num / den, theta_w = its norm (as
+ * s), and R <- exp(omega) R with exp(omega) = I + A [omega]x + B [omega]x^2,
+ * A = sin(theta_w) / theta_w and B = 2 sin^2(theta_w / 2) / theta_w^2 (1 -
+ * theta_w^2 / 6 and 1/2 - theta_w^2 / 24 below 1e-4).  A node without a
+ * passing entry keeps its R and counts omega = 0.  The sweeps end after the
+ * first one whose largest theta_w <= tol, where tol > 0, or after max_sweeps;
+ * tol = 0 runs exactly max_sweeps.  The largest theta_w is an integer maximum
+ * over the bits of the doubles, no float atomic; later launches test it on the
+ * device and the host looks every 8 sweeps.  One launch per sweep, no
+ * grid-wide barrier.  The log is ill-conditioned for an angle next to pi, so a
+ * threshold that admits such entries is allowed but not useful.
+ * Outputs, caller-allocated: R (N x 3 x 3); per edge (i, j), with P = R_rel R_i
+ * and t its trace sum against R_j: edge_inlier (E, 1 where t >= tau) and
+ * edge_angle (E) = atan2(s, (t - 1) / 2) in radians, s from M = P R_j^T as in
+ * stage 3; n_inlier_edges (N): a node's inlier edges; group (N): the connected
+ * component of the graph of inlier edges, labelled by its lowest node (host
+ * union-find after the download); info (N): 1 the root of a component with an
+ * edge, 0 another node with an inlier edge, -1 a node with none, the nodes
+ * without any edge included; level (N): the node's level in stage 1; *sweeps:
+ * the refit sweeps run.
+ * Gauge: the root of every component of the input graph is I.  The rotations
+ * inside one group are mutually consistent; a group that lost its inlier
+ * connection to its root keeps whatever offset the tree gave it, so a caller
+ * uses one group (the largest).
+ * Every output is the same from run to run: counts are integers, no sum
+ * depends on the order in which threads arrive.  N == 0 or E == 0 returns
+ * without touching a device (every R = I, every node its own group, info -1).
+ * sfm_last_timings: upload, kernels, download, the consensus kernels alone.
+ * ------------------------------------------------------------------- */
+int sfm_average_rotations(int32_t n_images, const int32_t *pair_ij, const double *R_rel, const double *weight,
+                          int64_t n_edges, uint64_t seed, double threshold, int32_t consensus_sweeps,
+                          int32_t max_sweeps, double tol, double *R, double *edge_angle, uint8_t *edge_inlier,
+                          int32_t *n_inlier_edges, int32_t *group, int32_t *info, int32_t *level, int32_t *sweeps,
+                          int device);
+
+/* ---------------------------------------------------------------------
  * Track merging: the rows of a match store that share a keypoint joined into
  * tracks, on the device.  A matching-file line lists only the direct matches
  * of one keypoint of its source image, so one scene point arrives as several

@@ -115,6 +115,8 @@ SIGNATURES = [
                                  ctypes.c_int32, _d, _d, _d, _i32, _i32, _i32, _i32, _u8, _i32, _i32, _d, _c]),
     ("sfm_init_pairs", _c, [_d, _i64, _i, _d, _d, _i, _d, _i32, _i, ctypes.c_double, ctypes.c_double, _d, _d, _i64,
                             _i32, _i32, _d, _i32, _i32, _d, _i32, _d, _u8, _d, _d, _i32, _d, _c]),
+    ("sfm_average_rotations", _c, [ctypes.c_int32, _i32, _d, _d, _i, ctypes.c_uint64, ctypes.c_double, ctypes.c_int32,
+                                   ctypes.c_int32, ctypes.c_double, _d, _d, _u8, _i32, _i32, _i32, _i32, _i32, _c]),
     ("sfm_merge_tracks", _c, [_i64, _i, _i32, _d, _d, _i, ctypes.c_int32, ctypes.c_int32, _i32, _i32, _u8, _i32, _i64,
                               _i32, _i64, _i32, _i32, _c]),
     ("sfm_match_descriptors", _c, [_u8, _i, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _i, ctypes.c_double,
@@ -1106,6 +1108,60 @@ def init_pairs(K, pair_start, x1, x2, F, hsamples=None, h_threshold=4.0, max_rep
     if want_hmodels:
         out += (hmodels.reshape(P, Hh, 3, 3),)
     return out
+
+
+def average_rotations(n_images, pair_ij, R_rel, weight=None, seed=0, threshold=np.deg2rad(5), consensus_sweeps=3,
+                      max_sweeps=200, tol=1e-9):
+    """Global rotation averaging (sfm_average_rotations): the rotation of every
+    one of ``n_images`` cameras from the relative rotations of the pairs, in one
+    device call.  ``pair_ij`` (E, 2): i != j, duplicates and both orientations
+    allowed; ``R_rel`` (E, 3, 3) under R_j ~ R_rel R_i with x_cam = R (X - C),
+    init_pairs' out[0][b] for pair_ij[b] = (i, j); ``weight`` (E,) finite and
+    > 0, or None for 1.  One spanning tree per component from its node of
+    highest degree (edge priorities from ``seed``), ``consensus_sweeps`` sweeps
+    in which every node takes the prediction that most of its other predictions
+    agree with to within ``threshold`` radians, then up to ``max_sweeps``
+    weighted refit sweeps over the agreeing entries, ended by the first whose
+    largest update is <= ``tol`` radians (tol = 0: exactly max_sweeps).
+    Returns (R (N, 3, 3), edge_angle (E,) radians, edge_inlier (E,) bool,
+    n_inlier_edges (N,) int32, group (N,) int32 the component of the inlier
+    graph labelled by its lowest node, info (N,) int32: 1 root, 0 has an inlier
+    edge, -1 none; level (N,) int32, sweeps int).  Gauge: the root of every
+    component of the input graph is I; rotations are mutually consistent inside
+    a group, and a group cut off from its root keeps an arbitrary offset, so use
+    one group.  The arguments are checked before a device is looked for
+    (SfmCoreError on a violation, with no output of the C call written);
+    n_images = 0 or no edge returns without one.  The threshold and the sweep
+    counts are policy defaults to override, not measured quantities."""
+    N = int(n_images)
+    ij = np.ascontiguousarray(pair_ij, dtype=np.int32).reshape(-1, 2)
+    E = len(ij)
+    Rr = _f64(R_rel)
+    if Rr.size != 9 * E:
+        raise ValueError("average_rotations: R_rel must be (E, 3, 3)")
+    Rr = Rr.reshape(E, 9)
+    w = None
+    if weight is not None:
+        w = _f64(weight).reshape(-1)
+        if len(w) != E:
+            raise ValueError("average_rotations: weight must be (E,)")
+    threshold, tol = float(threshold), float(tol)
+    consensus_sweeps, max_sweeps = int(consensus_sweeps), int(max_sweeps)
+    bad = (N < 0 or E > 1 << 30 or not (np.isfinite(threshold) and 0 < threshold < np.pi) or consensus_sweeps < 0
+           or max_sweeps < 0 or not tol >= 0
+           or bool(E and (ij.min() < 0 or ij.max() >= N or (ij[:, 0] == ij[:, 1]).any()))
+           or not bool(np.isfinite(Rr).all()) or (w is not None and not bool((np.isfinite(w) & (w > 0)).all())))
+    if not bad and N and E:
+        require_device()
+    n = max(N, 0)
+    R, angle, inlier = np.zeros((n, 9)), np.zeros(E), np.zeros(E, dtype=np.uint8)
+    n_inl, group, info, level = (np.zeros(n, dtype=np.int32) for _ in range(4))
+    sweeps = np.zeros(1, dtype=np.int32)
+    _check(_lib.sfm_average_rotations(N, _p(ij, _i32), _p(Rr), _p(w) if w is not None else None, E,
+                                      int(seed) & (2 ** 64 - 1), threshold, consensus_sweeps, max_sweeps, tol, _p(R),
+                                      _p(angle), _p(inlier, _u8), _p(n_inl, _i32), _p(group, _i32), _p(info, _i32),
+                                      _p(level, _i32), _p(sweeps, _i32), DEVICE))
+    return R.reshape(n, 3, 3), angle, inlier.astype(bool), n_inl, group, info, level, int(sweeps[0])
 
 
 MERGE_DROP, MERGE_KEEP_ROWS = 0, 1

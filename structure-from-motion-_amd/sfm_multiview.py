@@ -20,6 +20,11 @@ read.  ``init_pairs`` follows it: the pose, cheirality, parallax and
 homography support of every verified pair in one call (``sfm_init_pairs``), and
 from them the pair to start the reconstruction from.
 
+``pair_rotations`` and ``average_rotations`` use what ``init_pairs`` computes
+for every pair and the incremental chain then drops: all cameras' rotations at
+once from the relative rotations (``sfm_average_rotations``), with the mask of
+the pairs that are consistent around the loops of the view graph.
+
 ``merge_tracks`` comes before every one of them, right after read_matching: the
 store's rows that share a keypoint joined into tracks on the device
 (``sfm_merge_tracks``; sfm_io.merge_tracks, also MatchStore.merge_tracks).
@@ -245,6 +250,42 @@ def init_pairs(store, K, verified, Hh=128, seed=0, h_threshold=4.0, max_reproj=4
     out = _core.init_pairs(K, pair_start, x1, x2, F, hs, h_threshold=h_threshold, max_reproj=max_reproj)
     order, eligible = rank_initial_pairs(out, n_p, min_points, min_angle_deg, max_h_ratio)
     return order, eligible, out, pair_start, index1, index2
+
+
+def pair_rotations(verified, init, min_points=30):
+    """The edges of the view graph for ``average_rotations`` from what the chain
+    has already computed: ``verified`` is the tuple ``verify_pairs`` /
+    ``verify_pairs_calibrated`` returned, ``init`` the tuple ``init_pairs``
+    returned for it.  The pairs with init_pairs info == 0 and n_good >=
+    ``min_points`` are kept, in ``verified``'s order.
+    Returns (pair_ij (E, 2) int32, R_rel (E, 3, 3), weight (E,)): for the pair
+    (i, j) init_pairs' camera i is [I | 0] and camera j has R = out[0], so R_rel
+    is that R under R_j ~ R_rel R_i; the weight is n_good."""
+    pair_ij = np.asarray(verified[1], dtype=np.int32).reshape(-1, 2)
+    out = init[2]
+    n_good = np.asarray(out[4])
+    keep = (np.asarray(out[9]) == 0) & (n_good >= min_points)
+    return (np.ascontiguousarray(pair_ij[keep]), np.ascontiguousarray(np.asarray(out[0], dtype=np.float64)[keep]),
+            n_good[keep].astype(np.float64))
+
+
+def average_rotations(pair_ij, R_rel, n_images, weight=None, **args):
+    """Every camera's rotation from the pairs' relative rotations in one device
+    call (``_sfmcore.average_rotations``, which documents the algorithm, the
+    gauge and ``args``: seed, threshold, consensus_sweeps, max_sweeps, tol --
+    policy defaults to override, not measured quantities).
+    Returns (order, out): ``out`` is ``_sfmcore.average_rotations``'s tuple (R,
+    edge_angle, edge_inlier, n_inlier_edges, group, info, level, sweeps);
+    ``order`` lists the images of the largest group first (the lowest label on
+    ties), then the other groups by decreasing size, images ascending inside a
+    group.  Rotations are consistent inside one group only: R[order[:k]] with k
+    the size of the first group is the set to hand on, and edge_inlier says
+    which pairs agree with it."""
+    out = _core.average_rotations(n_images, pair_ij, R_rel, weight=weight, **args)
+    group = np.asarray(out[4], dtype=np.int64)
+    size = np.bincount(group, minlength=len(group))[group] if len(group) else group
+    order = np.lexsort((np.arange(len(group)), group, -size))
+    return order, out
 
 
 def _pair_bounds(store, verified):
