@@ -4,11 +4,18 @@ tests/test_match_descriptors.py and tests/golden/match_descriptors.npz.
 Integer work with an exact answer: every output is compared for equality, dtype
 and shape included; there are no tolerances.  Uniform random bytes are
 asymmetric data, so a swapped row or column or a k order that differs between
-the two MFMA operands cannot pass.
+the two MFMA operands cannot pass.  The last test reaches the kernels' pair
+stride: 65,535 + 600 pairs, so that 600 workgroups of k_md_nn, k_md_accept and
+k_md_write take a second pair of another shape than their first, against the
+vectorised restatement of tests/fast_refs.py (equal to the plain one wherever
+tests/test_fast_refs.py can afford the plain one).
 """
+import functools
+
 import numpy as np
 import pytest
 
+import fast_refs as fr
 import test_match_descriptors as md
 from test_match_descriptors import INT32_MAX
 
@@ -197,3 +204,39 @@ def test_fixture_scenes(core):
     for tag, desc, img_start, pairs, ratio, max_dsq, cross in md.fixture_cases():
         out = core.match_descriptors(desc, img_start, pairs, ratio, max_dsq, bool(cross), want_diagnostics=True)
         md.same(out, {n: fx[f"{tag}_{n}"] for n in md.OUTPUTS})
+
+
+@functools.lru_cache(maxsize=None)
+def wrap_neighbours(dim):
+    """the 66,135-pair scene of tests/fast_refs.py and what precedes the tests, once per dim"""
+    s = fr.wrap_scene(dim)
+    return s, fr.match_neighbours(s["desc"], s["img_start"], s["pairs"])
+
+
+def wrap_conditions(s, ref):
+    """what the scene must show for the comparison to mean something, from the restatement alone"""
+    ms, shape = ref["match_start"], s["shape"]
+    per = np.diff(ms)[fr.WRAP:]
+    busy = (shape[fr.WRAP:] > 0).all(axis=1)
+    assert (per > 0).sum() > 100 and ((per == 0) & busy).sum() > 10   # wrapped pairs with matches and with none
+    assert (np.diff(ms)[:fr.PLACED] > 0).sum() > 100
+    # match_start moves on each side of index 65,535: in the placed pairs, in the fillers and in the wrapped pairs
+    assert 0 < ms[fr.PLACED] < ms[fr.WRAP] < ms[-1] and len(np.unique(ms[fr.WRAP - 300:fr.WRAP + 300])) > 100
+    row = ref["row_off"][s["tie_pair"]] + 5
+    assert (ref["nn"][row], ref["d1"][row], ref["d2"][row]) == (3, 0, 0)  # the copies at 3 + T and 129 do not win
+
+
+@pytest.mark.parametrize("dim,cross_check", [(64, False), (64, True), (128, True)])
+def test_a_workgroup_takes_a_second_pair(core, dim, cross_check):
+    """gridDim.y is 65,535, so the workgroups of pairs 0 .. 599 go on to pairs 65,535 .. 66,134: every ordered
+    pair of (0, 1, 17, 65, 130, 2 BM + 9) keypoints as the rows of the first and of the second pair and as their
+    columns (tests/test_fast_refs.py asserts the table), a tie across column tiles in a second pair, and
+    match_start across the wrap.  Results left over from the first pair, rows of the second never written or a
+    barrier count that differs inside a workgroup cannot pass."""
+    s, nb = wrap_neighbours(dim)
+    ref = fr.match_accept(nb, 0.8, fr.wrap_limit(dim), cross_check)
+    ref.update(row_off=nb["row_off"])
+    wrap_conditions(s, ref)
+    out = core.match_descriptors(s["desc"], s["img_start"], s["pairs"], 0.8, fr.wrap_limit(dim), cross_check,
+                                 want_diagnostics=True)
+    md.same(out, ref)

@@ -3,11 +3,17 @@ sfm_io.match_descriptors_guided, sfm_multiview.rematch_verified) against the
 plain-numpy restatement of tests/test_match_guided.py and
 tests/golden/match_guided.npz.  The distances are integers and the gate is
 defined operation by operation in fp64, so every output is compared for
-equality, dtype and shape included; there are no tolerances.
+equality, dtype and shape included; there are no tolerances.  The last test
+reaches the kernels' pair stride: the 65,535 + 600 pairs of tests/fast_refs.py
+with an F of its own per pair and a finite gate, so that 600 workgroups reload
+F, the row terms and the candidate counters for a second pair, against the
+vectorised restatement there (equal to the plain one wherever
+tests/test_fast_refs.py can afford the plain one).
 """
 import numpy as np
 import pytest
 
+import fast_refs as fr
 import test_match_descriptors as md
 import test_match_guided as mg
 from test_match_descriptors import INT32_MAX
@@ -199,6 +205,32 @@ def test_fixture_scenes(core):
         out = core.match_descriptors_guided(desc, xy, img_start, pairs, F, gate, ratio, max_dsq, bool(cross),
                                             want_diagnostics=True)
         md.same(out, {n: fx[f"{tag}_{n}"] for n in mg.OUTPUTS}, mg.OUTPUTS)
+
+
+def test_a_workgroup_takes_a_second_pair_with_another_F(core):
+    """gridDim.y is 65,535, so the workgroups of pairs 0 .. 599 go on to pairs 65,535 .. 66,134, of other shapes
+    (tests/test_fast_refs.py asserts the table) and each with an F of its own under a finite gate: an F, row terms
+    or candidate counters left over from the workgroup's first pair change n_cand, and with it nn, of the second"""
+    s = fr.wrap_scene(64)
+    ref = fr.match_guided(s["desc"], s["xy"], s["img_start"], s["pairs"], s["F"], fr.GUIDED_GATE, 0.8,
+                          fr.wrap_limit(64), True)
+    # conditions on the inputs, from the restatement alone
+    ni, nj = s["shape"][:, 0], s["shape"][:, 1]
+    pair = np.repeat(np.arange(len(ni)), ni)
+    short = np.bincount(pair, weights=ref["n_cand"] < nj[pair], minlength=len(ni))  # rows with a candidate refused
+    some = np.bincount(pair, weights=ref["n_cand"] > 0, minlength=len(ni))
+    busy = (ni > 0) & (nj > 0)
+    wrapped = np.arange(len(ni)) >= fr.WRAP
+    assert (wrapped & busy & (short > 0) & (some > 0)).sum() > 100  # wrapped pairs with candidates refused ...
+    assert (wrapped & busy & (short == 0)).sum() >= 5               # ... and with every candidate admitted
+    per = np.diff(ref["match_start"])
+    assert (per[fr.WRAP:] > 0).sum() > 50 and ((per[fr.WRAP:] == 0) & busy[fr.WRAP:]).sum() > 50
+    assert 0 < ref["match_start"][fr.WRAP] < ref["match_start"][-1]
+    lo = int(ni[:s["nan_pair"]].sum())
+    assert ni[s["nan_pair"]] > 0 and (ref["n_cand"][lo:lo + ni[s["nan_pair"]]] == 0).all()  # the F with a NaN
+    out = core.match_descriptors_guided(s["desc"], s["xy"], s["img_start"], s["pairs"], s["F"], fr.GUIDED_GATE, 0.8,
+                                        fr.wrap_limit(64), True, want_diagnostics=True)
+    md.same(out, ref, mg.OUTPUTS)
 
 
 def test_twins_are_recovered_through_the_python_layer(core):

@@ -2,11 +2,21 @@
 sfm_select_pairs, sfm_io.select_pairs) against the plain-numpy restatement of
 tests/test_retrieval.py and tests/golden/retrieval.npz.  Integer work with an
 exact answer, and a score of five IEEE operations: every output is compared
-for equality, dtype and shape included; there are no tolerances.
+for equality, dtype and shape included; there are no tolerances.  The last two
+tests reach the second regimes: training on 2^20 + 300 rows (two pseudo-images
+of the nearest-centre pass, the tally's grid stride, the sort and the sums at a
+million rows, an inertia above 2^32) and retrieval at 513, 6,145, 8,193 and
+16,384 images (the top-k scan's stride, the dynamic-LDS attribute above 48 KiB,
+a launch above 64 KiB and the documented limit), against the vectorised
+restatements of tests/fast_refs.py (equal to the plain ones wherever
+tests/test_fast_refs.py can afford the plain ones).
 """
+import functools
+
 import numpy as np
 import pytest
 
+import fast_refs as fr
 import test_retrieval as rt
 from test_retrieval import N_WORDS, SELECT_OUTPUTS, TRAIN_OUTPUTS
 
@@ -143,6 +153,52 @@ def test_select_pairs_of_one_image_and_of_many_short_ones(core):
     top = ref["score"][:, :-1]
     assert ((top == ref["score"][:, 1:]) & (top > 0)).any()  # a condition on the inputs: tied scores exist
     check_select(core, word, np.arange(0, 351, 5), 50, 80)   # top_k above the image count
+
+
+@functools.lru_cache(maxsize=None)
+def large_training():
+    """the scene of 2^20 + 300 rows and its restatement after one update, which holds the quantisation too"""
+    desc, centres = fr.train_scene()
+    return desc, centres, fr.train(desc, centres, 1)
+
+
+@pytest.mark.parametrize("its", [0, 1])
+def test_training_past_one_pseudo_image(core, its):
+    """2^20 + 300 descriptors at dim 64 against 65 centres: the nearest-centre pass takes the rows as a block of
+    2^20 and a block of 300 whose results start at row 2^20, k_vt_tally strides its grid, and the sort, the byte
+    sums and the u64 inertia see a million rows"""
+    desc, centres, one = large_training()
+    ref = one
+    if its == 0:  # the state before the update: the assignment to the initial centres
+        word, count, total = fr.assign(desc, centres)
+        ref = dict(centres=centres, word=word.astype(np.int32), count=count, inertia=np.array([total], np.int64),
+                   iterations=np.int32(0))
+        assert total == one["inertia"][0]
+    # conditions on the inputs, from the restatement alone
+    tail, head = ref["word"][2 ** 20:], ref["word"][:300]
+    assert len(tail) == 300 and len(np.unique(tail)) > 30 and (tail != head).sum() > 250
+    assert (ref["inertia"] > 2 ** 32).all() and ref["count"].sum() == len(desc) and ref["count"].min() > 0
+    assert int(ref["iterations"]) == its and len(ref["inertia"]) == its + 1
+    assert its == 0 or (ref["inertia"][1] < ref["inertia"][0] and not np.array_equal(ref["centres"], centres))
+    rt.same(train(core, desc, centres, its), ref, TRAIN_OUTPUTS)
+
+
+@pytest.mark.parametrize("n_images", fr.SELECT_SIZES)
+def test_select_pairs_at_the_four_lds_regimes(core, n_images):
+    """one image more than the query workgroup has threads, then 49,288, 65,672 and 131,200 bytes of dynamic LDS:
+    above 48 KiB, above 64 KiB and at the 16,384 images the header allows"""
+    word, img_start = fr.select_scene(n_images)
+    ref = fr.select(word, img_start, fr.SELECT_WORDS, fr.SELECT_TOP_K)
+    # conditions on the inputs, from the restatement alone
+    nb, sc = ref["neighbour"], ref["score"]
+    assert ((sc[:, :-1] == sc[:, 1:]) & (sc[:, :-1] > 0)).any()                 # tied scores exist
+    ahead = [(nb[:, a] >= fr.SP_THREADS) & (nb[:, b] >= 0) & (nb[:, b] < fr.SP_THREADS)
+             for a in range(fr.SELECT_TOP_K) for b in range(a + 1, fr.SELECT_TOP_K)]
+    assert np.any(ahead)  # an index that only the scan's stride reaches ranks ahead of one that its start reaches
+    assert nb[fr.SELECT_TWIN, 0] == n_images - 1 and nb[fr.SELECT_TWIN, 1] >= 0
+    assert (nb[n_images // 2] == -1).all() and (nb == -1).any(axis=1).sum() >= 1  # padded rows
+    assert (nb >= 0).all(axis=1).sum() > n_images // 2
+    rt.same(core.select_pairs(word, img_start, fr.SELECT_WORDS, fr.SELECT_TOP_K), ref, SELECT_OUTPUTS)
 
 
 def test_python_layer_returns_the_within_group_pairs(core, fx):
