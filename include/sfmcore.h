@@ -30,7 +30,8 @@ enum {
     SFM_ERR_NOMEM = -3,   /* device allocation failed                    */
     SFM_ERR_SOLVE = -4,   /* reduced camera system not positive definite */
     SFM_ERR_COMM = -5,    /* RCCL error                                  */
-    SFM_ERR_CAPACITY = -6 /* a result exceeds the caller's output arrays */
+    SFM_ERR_CAPACITY = -6, /* a result exceeds the caller's output arrays */
+    SFM_ERR_NUMERIC = -7   /* an iterate left the range a stage defines    */
 };
 
 int sfm_version(void);
@@ -730,6 +731,92 @@ int sfm_average_rotations(int32_t n_images, const int32_t *pair_ij, const double
                           int32_t max_sweeps, double tol, double *R, double *edge_angle, uint8_t *edge_inlier,
                           int32_t *n_inlier_edges, int32_t *group, int32_t *info, int32_t *level, int32_t *sweeps,
                           int device);
+
+/* ---------------------------------------------------------------------
+ * Global position averaging: the centre of every camera from the directions
+ * between the cameras of the pairs, in one call -- rounds of a preconditioned
+ * conjugate-gradient solve with reweighting between them.  sfm_init_pairs gives
+ * a unit baseline for every verified pair and sfm_average_rotations every
+ * camera's rotation; together they give the direction of every pair in world
+ * coordinates, and this turns all of them into centres, with an edge mask.  The
+ * reference has no counterpart.
+ * n_images = N >= 0 cameras; the n_edges = E >= 0 edges are pair_ij (E x 2
+ * int32: i != j, both in [0, N); duplicate pairs and both orientations of a
+ * pair are allowed, each is an edge of its own) with dir (E x 3 fp64): the
+ * direction from C_i towards C_j in world coordinates, finite and not zero; the
+ * host divides it by its largest |component| and then by its norm, d_e below is
+ * the result.  weight (E, finite and > 0) is nullable: every weight 1.
+ * 0 < mu <= 1; sigma finite, > 0, radians; threshold finite, in (0, pi),
+ * radians; rounds >= 1; cg_tol finite, >= 0; cg_max_iters >= 1; path 0, 1 or
+ * 2; E <= 2^30.  A violation is SFM_ERR_ARG, found on the host before a device
+ * is looked for, with nothing written; so is path = 1 with more than
+ * SFM_POSITIONS_PATH1_MAX_NODES solved nodes.
+ * The graph that is solved (host): a node's entries are the edges that contain
+ * it, by ascending edge index.  Nodes with fewer than 2 distinct neighbours are
+ * dropped, again and again until none is left: the distance of a leaf along
+ * its one direction is undetermined.  Of what remains only the largest
+ * connected component (union-find; most nodes, the one with the lowest node on
+ * ties) is solved: its M nodes, the "solved" ones, and the edges between them.
+ * The root is the solved node with the most entries among those edges, the
+ * lowest index on ties.  Parallel rigidity beyond this is not checked; a graph
+ * that is not rigid shows as solves that end at cg_max_iters.
+ * A round has a weight w_e and a target length s_e per edge; round 0 has
+ * w_e = weight_e and s_e = 1.  With v_e = C_j - C_i it minimises
+ *   sum_e w_e ( |v_e - d_e (d_e.v_e)|^2 + mu (d_e.v_e - s_e)^2 )
+ * over the centres with the root at 0: the linear system A x = b over the
+ * other M - 1 nodes with the 3 x 3 blocks
+ *   off-diagonal, per entry of n with neighbour m:  -w_e (I - (1 - mu) d_e d_e^T),
+ *   diagonal D_n: the sum of w_e (I - (1 - mu) d_e d_e^T) over n's entries,
+ *   b_n: the sum over n's entries of +mu w_e s_e d_e where n is the edge's j and
+ *        -mu w_e s_e d_e where it is the edge's i.
+ * mu = 0 would be the chordal cost, singular on exact data; mu > 0 fixes the
+ * scale and bounds the condition number, and since the targets follow the
+ * iterate the fixed point carries no length bias.  D_n >= mu (sum w) I is
+ * always invertible (by cofactors).
+ * A solve: conjugate gradients preconditioned by the D_n^-1, the operator
+ * applied from the adjacency as q_n = sum over n's entries of
+ * w_e (u - (1 - mu) d_e (d_e.u)), u = p_n - p_m (the root's p is 0):
+ *   x = x0 (0 in round 0, then the normalised centres of the round before);
+ *   r = b - A x; z = D^-1 r; p = z; rho = r.z; k = 0;
+ *   while k < cg_max_iters and |r| > cg_tol |b|:
+ *     q = A p; alpha = rho / p.q; x += alpha p; r -= alpha q; z = D^-1 r;
+ *     rho' = r.z; p = z + (rho' / rho) p; rho = rho'; k += 1
+ *   cg_iters[round] = k; cg_residual[round] = |r| / |b| (0 where |b| = 0).
+ * After the solve c = sum_e w_e (d_e.v_e) / sum_e w_e on the round's weights;
+ * c not finite or <= 0 ends the call with SFM_ERR_NUMERIC (every output 0, info
+ * -1).  Every centre is divided by c, and on the divided centres, per edge:
+ *   l = |v_e|; theta_e = atan2(|d_e x v_e|, d_e.v_e);
+ *   s_e <- max(d_e.v_e, 1e-3);
+ *   w_e <- weight_e / ((1 + (theta_e / sigma)^2) max(l, 1e-3)^2).
+ * `rounds` rounds run; the outputs are those of the last solve and its division.
+ * Outputs, caller-allocated: C (N x 3), 0 for a node that was not solved;
+ * edge_angle (E) = theta_e, edge_length (E) = d_e.v_e, edge_inlier (E) = 1 where
+ * theta_e <= threshold -- all three 0 for an edge with an endpoint that was not
+ * solved; info (N): 1 the root, 0 another solved node, -1 a node not solved;
+ * cg_iters and cg_residual (rounds each); *n_solved = M; *path_used: 1 or 2, 0
+ * where no device was used.  Gauge: the root is at 0 and the weighted mean of
+ * d_e.v_e is 1, so the scale is arbitrary.  N == 0, E == 0 or M == 0 returns
+ * without touching a device.
+ * Device, fp64.  path = 1: one workgroup, one launch for all rounds; x, r, p,
+ * z, q and the six distinct entries of every D_n^-1 live in LDS, 168 bytes a
+ * node, which with the static 64 KB would stop near 390 nodes; with dynamic LDS
+ * the bound is SFM_POSITIONS_PATH1_MAX_NODES = 512 solved nodes (86,208 bytes),
+ * the root included.  path = 2: any size, two launches per CG iteration and no
+ * grid-wide barrier; the stop is tested on the device and read by the host
+ * every 8 iterations.  path = 0 takes path 1 where M fits and path 2 otherwise.
+ * On either path a node's entries are walked by G lanes (a power of two, 1 ..
+ * 64) whose partial sums meet in a fixed tree, and every sum over nodes or edges
+ * is a fixed tree too: no float atomics, every output bit-identical from run
+ * to run on one path.  The two paths add in different orders, so they agree
+ * with each other (and with a dense solve) to a tolerance, not bitwise.
+ * sfm_last_timings: upload, kernels, download, the CG iterations alone.
+ * ------------------------------------------------------------------- */
+#define SFM_POSITIONS_PATH1_MAX_NODES 512
+int sfm_average_positions(int32_t n_images, const int32_t *pair_ij, const double *dir, const double *weight,
+                          int64_t n_edges, double mu, double sigma, double threshold, int32_t rounds, double cg_tol,
+                          int32_t cg_max_iters, int32_t path, double *C, double *edge_angle, uint8_t *edge_inlier,
+                          double *edge_length, int32_t *info, int32_t *cg_iters, double *cg_residual,
+                          int32_t *n_solved, int32_t *path_used, int device);
 
 /* ---------------------------------------------------------------------
  * Track merging: the rows of a match store that share a keypoint joined into

@@ -117,6 +117,9 @@ SIGNATURES = [
                             _i32, _i32, _d, _i32, _i32, _d, _i32, _d, _u8, _d, _d, _i32, _d, _c]),
     ("sfm_average_rotations", _c, [ctypes.c_int32, _i32, _d, _d, _i, ctypes.c_uint64, ctypes.c_double, ctypes.c_int32,
                                    ctypes.c_int32, ctypes.c_double, _d, _d, _u8, _i32, _i32, _i32, _i32, _i32, _c]),
+    ("sfm_average_positions", _c, [ctypes.c_int32, _i32, _d, _d, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _d, _d, _u8, _d,
+                                   _i32, _i32, _d, _i32, _i32, _c]),
     ("sfm_merge_tracks", _c, [_i64, _i, _i32, _d, _d, _i, ctypes.c_int32, ctypes.c_int32, _i32, _i32, _u8, _i32, _i64,
                               _i32, _i64, _i32, _i32, _c]),
     ("sfm_match_descriptors", _c, [_u8, _i, _i64, ctypes.c_int32, ctypes.c_int32, _i32, _i, ctypes.c_double,
@@ -1162,6 +1165,63 @@ def average_rotations(n_images, pair_ij, R_rel, weight=None, seed=0, threshold=n
                                       _p(angle), _p(inlier, _u8), _p(n_inl, _i32), _p(group, _i32), _p(info, _i32),
                                       _p(level, _i32), _p(sweeps, _i32), DEVICE))
     return R.reshape(n, 3, 3), angle, inlier.astype(bool), n_inl, group, info, level, int(sweeps[0])
+
+
+POSITIONS_PATH1_MAX_NODES = 512  # SFM_POSITIONS_PATH1_MAX_NODES
+
+
+def average_positions(n_images, pair_ij, dir, weight=None, mu=0.01, sigma=np.deg2rad(3), threshold=np.deg2rad(5),
+                      rounds=12, cg_tol=1e-12, cg_max_iters=2000, path=0):
+    """Global position averaging (sfm_average_positions): the centre of every
+    one of ``n_images`` cameras from the directions between the cameras of the
+    pairs, in one device call.  ``pair_ij`` (E, 2): i != j, duplicates and both
+    orientations allowed; ``dir`` (E, 3): the direction from C_i towards C_j in
+    world coordinates, finite and not zero (normalised by the call); ``weight``
+    (E,) finite and > 0, or None for 1.  Nodes with fewer than two distinct
+    neighbours are pruned repeatedly and the largest component of the rest is
+    solved.  ``rounds`` rounds, each a conjugate-gradient solve (preconditioned
+    by the 3 x 3 diagonal blocks, ended at a relative residual of ``cg_tol`` or
+    after ``cg_max_iters`` iterations) of the chordal cost with the term
+    ``mu`` (d.v - s)^2 that pins the lengths, a division by the weighted mean
+    baseline, and new weights weight / ((1 + (theta / ``sigma``)^2) |v|^2).
+    ``path``: 1 the single-workgroup kernel (at most POSITIONS_PATH1_MAX_NODES
+    solved nodes), 2 the multi-launch one, 0 whichever fits.
+    Returns (C (N, 3), edge_angle (E,) radians, edge_inlier (E,) bool: angle <=
+    ``threshold``, edge_length (E,) = d.(C_j - C_i), info (N,) int32: 1 root, 0
+    solved, -1 not solved; cg_iters (rounds,) int32, cg_residual (rounds,),
+    n_solved int, path_used int).  C and the edge outputs are 0 for what was not
+    solved.  Gauge: the root at 0, the weighted mean of d.(C_j - C_i) equal to 1;
+    the scale is arbitrary.  A solve that ends at cg_max_iters is reported in
+    cg_iters, not raised: a graph that is not rigid shows there.  The arguments
+    are checked before a device is looked for (SfmCoreError on a violation, with
+    no output of the C call written); nothing to solve returns without one.
+    The parameters are policy defaults to override, not measured optima."""
+    N = int(n_images)
+    ij = np.ascontiguousarray(pair_ij, dtype=np.int32).reshape(-1, 2)
+    E = len(ij)
+    d = _f64(dir)
+    if d.size != 3 * E:
+        raise ValueError("average_positions: dir must be (E, 3)")
+    d = d.reshape(E, 3)
+    w = None
+    if weight is not None:
+        w = _f64(weight).reshape(-1)
+        if len(w) != E:
+            raise ValueError("average_positions: weight must be (E,)")
+    mu, sigma, threshold, cg_tol = float(mu), float(sigma), float(threshold), float(cg_tol)
+    rounds, cg_max_iters, path = int(rounds), int(cg_max_iters), int(path)
+    n, nr = max(N, 0), max(rounds, 0)
+    C, angle, inlier, length = np.zeros((n, 3)), np.zeros(E), np.zeros(E, dtype=np.uint8), np.zeros(E)
+    info, iters, resid = np.zeros(n, dtype=np.int32), np.zeros(nr, dtype=np.int32), np.zeros(nr)
+    n_solved, path_used = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+
+    # the library checks the arguments and prunes the graph before it looks for a device: only a call that passes
+    # both and has something to solve needs one, and fails loudly without it (no CPU fallback)
+    _check(_lib.sfm_average_positions(N, _p(ij, _i32), _p(d), _p(w) if w is not None else None, E, mu, sigma,
+                                      threshold, rounds, cg_tol, cg_max_iters, path, _p(C), _p(angle), _p(inlier, _u8),
+                                      _p(length), _p(info, _i32), _p(iters, _i32), _p(resid), _p(n_solved, _i32),
+                                      _p(path_used, _i32), DEVICE))
+    return (C, angle, inlier.astype(bool), length, info, iters, resid, int(n_solved[0]), int(path_used[0]))
 
 
 MERGE_DROP, MERGE_KEEP_ROWS = 0, 1

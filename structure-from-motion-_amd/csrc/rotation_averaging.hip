@@ -33,9 +33,9 @@
 // order, so the outputs do not depend on how the work is spread.
 #include <cmath>
 #include <cstring>
-#include <numeric>
 
 #include "staging.hpp"
+#include "view_graph.hpp"
 
 namespace sfm {
 
@@ -293,22 +293,6 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_edges(const int32_t *__restri
     edge_inlier[e] = t >= tau ? 1 : 0;
 }
 
-// union-find over int32 nodes: the root of a set is its lowest node
-struct RaSets {
-    std::vector<int32_t> parent;
-    explicit RaSets(int32_t n) : parent((size_t)n) { std::iota(parent.begin(), parent.end(), 0); }
-    int32_t find(int32_t x) {
-        while (parent[x] != x) x = parent[x] = parent[parent[x]];
-        return x;
-    }
-    void join(int32_t a, int32_t b) {
-        a = find(a);
-        b = find(b);
-        if (a < b) parent[b] = a;
-        else parent[a] = b;
-    }
-};
-
 }  // namespace sfm
 
 using namespace sfm;
@@ -340,27 +324,13 @@ extern "C" int sfm_average_rotations(int32_t n_images, const int32_t *pair_ij, c
     *sweeps = 0;
     if (N == 0) return 0;
     // adjacency: both endpoints of every edge, ascending e inside a node
-    std::vector<int64_t> adj_start((size_t)N + 1, 0);
-    for (int64_t e = 0; e < E; ++e) {
-        ++adj_start[(size_t)pair_ij[2 * e] + 1];
-        ++adj_start[(size_t)pair_ij[2 * e + 1] + 1];
-    }
-    for (int32_t n = 0; n < N; ++n) adj_start[(size_t)n + 1] += adj_start[n];
-    std::vector<int32_t> ent_code((size_t)(2 * E)), ent_nbr((size_t)(2 * E));
-    {
-        std::vector<int64_t> fill(adj_start.begin(), adj_start.end() - 1);
-        for (int64_t e = 0; e < E; ++e) {
-            const int32_t i = pair_ij[2 * e], j = pair_ij[2 * e + 1];
-            ent_code[(size_t)fill[i]] = (int32_t)(2 * e);  // fwd: R_i = R_rel^T R_j
-            ent_nbr[(size_t)fill[i]++] = j;
-            ent_code[(size_t)fill[j]] = (int32_t)(2 * e + 1);  // rev: R_j = R_rel R_i
-            ent_nbr[(size_t)fill[j]++] = i;
-        }
-    }
+    std::vector<int64_t> adj_start;
+    std::vector<int32_t> ent_code, ent_nbr;  // fwd: R_i = R_rel^T R_j; rev: R_j = R_rel R_i
+    build_adjacency(N, pair_ij, E, adj_start, ent_code, ent_nbr);
     // components of the input graph and their roots: highest degree, lowest index on ties
     std::vector<int32_t> root_of((size_t)N), is_root((size_t)N, 0);
     {
-        RaSets sets(N);
+        NodeSets sets(N);
         for (int64_t e = 0; e < E; ++e) sets.join(pair_ij[2 * e], pair_ij[2 * e + 1]);
         std::vector<int32_t> best((size_t)N, -1);
         for (int32_t n = 0; n < N; ++n) {
@@ -517,7 +487,7 @@ extern "C" int sfm_average_rotations(int32_t n_images, const int32_t *pair_ij, c
     *sweeps = n_run;
 
     // the inlier graph: counts, groups, info
-    RaSets sets(N);
+    NodeSets sets(N);
     for (int32_t n = 0; n < N; ++n) n_inlier_edges[n] = 0;
     for (int64_t e = 0; e < E; ++e) {
         if (!edge_inlier[e]) continue;

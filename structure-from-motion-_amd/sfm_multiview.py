@@ -25,6 +25,12 @@ for every pair and the incremental chain then drops: all cameras' rotations at
 once from the relative rotations (``sfm_average_rotations``), with the mask of
 the pairs that are consistent around the loops of the view graph.
 
+``pair_directions`` and ``average_positions`` are the other half of that global
+path: the pairs' baselines turned into world directions by the averaged
+rotations, and all camera centres at once from them
+(``sfm_average_positions``), so that triangulation and bundle adjustment can
+start with every camera.
+
 ``merge_tracks`` comes before every one of them, right after read_matching: the
 store's rows that share a keypoint joined into tracks on the device
 (``sfm_merge_tracks``; sfm_io.merge_tracks, also MatchStore.merge_tracks).
@@ -286,6 +292,50 @@ def average_rotations(pair_ij, R_rel, n_images, weight=None, **args):
     size = np.bincount(group, minlength=len(group))[group] if len(group) else group
     order = np.lexsort((np.arange(len(group)), group, -size))
     return order, out
+
+
+def pair_directions(verified, init, rotations, min_points=30):
+    """The edges of the view graph for ``average_positions``: ``verified`` and
+    ``init`` as for ``pair_rotations``, ``rotations`` the (order, out) that
+    ``average_rotations`` returned for ``pair_rotations(verified, init,
+    min_points)``.  Of the pairs ``pair_rotations`` keeps (the same rule, the
+    same order), those stay whose ``edge_inlier`` is set and whose two images
+    both lie in the first group of ``order``.
+    Returns (pair_ij (E, 2) int32, dir (E, 3), weight (E,), keep): ``keep`` (P,)
+    bool marks the pairs of ``verified`` taken.  For the pair (i, j) init_pairs'
+    camera i is [I | 0] and out[1] is C_rel, the centre of camera j in camera
+    i's frame (x_cam = R (X - C)); with the averaged R_i the world direction
+    from C_i to C_j is dir = R_i^T C_rel.  The weight is n_good."""
+    pair_ij = np.asarray(verified[1], dtype=np.int32).reshape(-1, 2)
+    out = init[2]
+    n_good = np.asarray(out[4])
+    usable = (np.asarray(out[9]) == 0) & (n_good >= min_points)
+    order, rot = rotations
+    R, inlier, group = np.asarray(rot[0]), np.asarray(rot[2], dtype=bool), np.asarray(rot[4])
+    if len(inlier) != int(usable.sum()):
+        raise ValueError("pair_directions: rotations do not belong to pair_rotations(verified, init, min_points)")
+    in_first = group == group[order[0]] if len(order) else np.zeros(0, dtype=bool)
+    keep = usable.copy()
+    keep[usable] = inlier & in_first[pair_ij[usable, 0]] & in_first[pair_ij[usable, 1]]
+    C_rel = np.asarray(out[1], dtype=np.float64).reshape(-1, 3)[keep]
+    dirs = np.einsum("eji,ej->ei", R[pair_ij[keep, 0]], C_rel)
+    return np.ascontiguousarray(pair_ij[keep]), np.ascontiguousarray(dirs), n_good[keep].astype(np.float64), keep
+
+
+def average_positions(pair_ij, dir, n_images, weight=None, **args):
+    """Every camera's centre from the pairs' world directions in one device call
+    (``_sfmcore.average_positions``, which documents the algorithm and ``args``:
+    mu, sigma, threshold, rounds, cg_tol, cg_max_iters, path -- policy defaults
+    to override, not measured optima).
+    Returns (solved, out): ``out`` is ``_sfmcore.average_positions``'s tuple (C,
+    edge_angle, edge_inlier, edge_length, info, cg_iters, cg_residual, n_solved,
+    path_used); ``solved`` lists, ascending, the images with info >= 0 -- those
+    of the largest component left after leaf pruning, the only ones with a
+    centre.  Gauge: the root (info == 1) is at 0 and the weighted mean baseline
+    d.(C_j - C_i) is 1, so the scale is arbitrary and the frame is that of the
+    rotations the directions were formed with."""
+    out = _core.average_positions(n_images, pair_ij, dir, weight=weight, **args)
+    return np.flatnonzero(np.asarray(out[4]) >= 0), out
 
 
 def _pair_bounds(store, verified):
