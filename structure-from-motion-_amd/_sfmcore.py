@@ -853,9 +853,7 @@ def register_samples(counts, H, seed):
 
 def p3p_samples(counts, H, seed):
     """The 3-point sample table of register_views_p3p: (V, H, 3) int32, drawn
-    as register_samples draws -- view v from child v of
-    numpy.random.default_rng(seed), the rows that hold a duplicate redrawn until
-    none do; a view of n_v < 3 gets zeros."""
+    as register_samples draws (_sample_tables); a view of n_v < 3 gets zeros."""
     return _sample_tables(counts, H, seed, 3, "p3p_samples")
 
 
@@ -884,12 +882,31 @@ def _sample_tables(counts, H, seed, k, who):
     return out
 
 
+def _rows_rejected(bad, start, n_items, samples=None, min_n=0, live_n=None):
+    """Whether the C call of a hypothesis-batch entry point will reject its
+    arguments: ``bad`` (what the caller found already), CSR row starts that do
+    not run from 0 to ``n_items``, or ``samples`` (rows, H, k) that leave [0, n)
+    or repeat an entry in a row of at least ``min_n`` items.  Where it will not
+    and some row has ``live_n`` (default ``min_n``) items: require_device()."""
+    if bad or start[0] != 0 or bool(np.any(np.diff(start) < 0)) or start[-1] != n_items:
+        return True
+    n = np.diff(start)
+    rows = n >= min_n
+    if samples is not None and rows.any():
+        s = samples[rows]
+        srt = np.sort(s, axis=2)
+        if ((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n[rows]).any()
+                or (srt[:, :, 1:] == srt[:, :, :-1]).any()):
+            return True
+    if (n >= (min_n if live_n is None else live_n)).any():
+        require_device()
+    return False
+
+
 def pair_samples(counts, H, seed):
     """The 8-point sample table of verify_pairs for pairs of ``counts``
-    correspondences: (P, H, 8) int32, drawn as register_samples draws -- pair p
-    from child p of numpy.random.default_rng(seed), the rows that hold a
-    duplicate redrawn until none do, so a pair's table does not depend on the
-    other pairs; a pair of n_p < 8 gets zeros."""
+    correspondences: (P, H, 8) int32, drawn as register_samples draws
+    (_sample_tables); a pair of n_p < 8 gets zeros."""
     return _sample_tables(counts, H, seed, 8, "pair_samples")
 
 
@@ -922,18 +939,8 @@ def verify_pairs(pair_start, x1, x2, samples, threshold=2.5, min_inliers=8, refi
         raise ValueError("verify_pairs: samples must be (P, H, 8) with H >= 1")
     H = samples.shape[1]
     threshold = float(threshold)
-    bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 8 or int(refit_rounds) < 0
-           or ps[0] != 0 or bool(np.any(np.diff(ps) < 0)) or ps[-1] != len(x1))
-    if not bad:
-        n_p = np.diff(ps)
-        live = n_p >= 8
-        if live.any():
-            s = samples[live]
-            srt = np.sort(s, axis=2)
-            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_p[live]).any()
-                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
-            if not bad:
-                require_device()
+    _rows_rejected(not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 8 or int(refit_rounds) < 0,
+                   ps, len(x1), samples, 8)
     F, cost = np.zeros((P, 9)), np.zeros(P)
     n_inl, hyp, count, info = (np.zeros(P, dtype=np.int32) for _ in range(4))
     inlier = np.zeros(len(x1), dtype=np.uint8)
@@ -953,10 +960,8 @@ def verify_pairs(pair_start, x1, x2, samples, threshold=2.5, min_inliers=8, refi
 
 def essential_samples(counts, H, seed):
     """The 5-point sample table of essential_pairs for pairs of ``counts``
-    correspondences: (P, H, 5) int32, drawn as pair_samples draws -- pair p from
-    child p of numpy.random.default_rng(seed), the rows that hold a duplicate
-    redrawn until none do, so a pair's table does not depend on the other
-    pairs; a pair of n_p < 5 gets zeros."""
+    correspondences: (P, H, 5) int32, drawn as register_samples draws
+    (_sample_tables); a pair of n_p < 5 gets zeros."""
     return _sample_tables(counts, H, seed, 5, "essential_samples")
 
 
@@ -996,18 +1001,8 @@ def essential_pairs(K, pair_start, x1, x2, samples, threshold=2.5, min_inliers=5
     threshold = float(threshold)
     with np.errstate(all="ignore"):
         bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < 5 or int(refit_rounds) < 0
-               or int(max_nfev) <= 0 or not np.all(np.isfinite(K)) or not np.linalg.det(K.reshape(3, 3)) != 0
-               or ps[0] != 0 or bool(np.any(np.diff(ps) < 0)) or ps[-1] != len(x1))
-    if not bad:
-        n_p = np.diff(ps)
-        live = n_p >= 5
-        if live.any():
-            s = samples[live]
-            srt = np.sort(s, axis=2)
-            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_p[live]).any()
-                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
-            if not bad:
-                require_device()
+               or int(max_nfev) <= 0 or not np.all(np.isfinite(K)) or not np.linalg.det(K.reshape(3, 3)) != 0)
+    _rows_rejected(bad, ps, len(x1), samples, 5)
     E, F, cost = np.zeros((P, 9)), np.zeros((P, 9)), np.zeros(P)
     n_inl, hyp, count, info = (np.zeros(P, dtype=np.int32) for _ in range(4))
     inlier = np.zeros(len(x1), dtype=np.uint8)
@@ -1029,10 +1024,8 @@ def essential_pairs(K, pair_start, x1, x2, samples, threshold=2.5, min_inliers=5
 
 def homography_samples(counts, H, seed):
     """The 4-point sample table of init_pairs for pairs of ``counts``
-    correspondences: (P, H, 4) int32, drawn as pair_samples draws -- pair p from
-    child p of numpy.random.default_rng(seed), the rows that hold a duplicate
-    redrawn until none do, so a pair's table does not depend on the other
-    pairs; a pair of n_p < 4 gets zeros."""
+    correspondences: (P, H, 4) int32, drawn as register_samples draws
+    (_sample_tables); a pair of n_p < 4 gets zeros."""
     return _sample_tables(counts, H, seed, 4, "homography_samples")
 
 
@@ -1078,17 +1071,9 @@ def init_pairs(K, pair_start, x1, x2, F, hsamples=None, h_threshold=4.0, max_rep
             hsamples = None
     h_threshold, max_reproj = float(h_threshold), float(max_reproj)
     bad = (not (np.isfinite(h_threshold) and h_threshold > 0) or not (np.isfinite(max_reproj) and max_reproj > 0)
-           or Hh > 1 << 20 or ps[0] != 0 or bool(np.any(np.diff(ps) < 0)) or ps[-1] != len(x1))
-    if not bad:
-        n_p = np.diff(ps)
-        sampled = n_p >= 4
-        if Hh and sampled.any():
-            s = hsamples[sampled]
-            srt = np.sort(s, axis=2)
-            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_p[sampled]).any()
-                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
-        if not bad and (n_p >= 8).any():
-            require_device()
+           or Hh > 1 << 20)
+    # a pair of four is sampled, a pair of eight is live
+    _rows_rejected(bad, ps, len(x1), hsamples if Hh else None, 4, live_n=8)
     R, C, med, Hbest = np.zeros((P, 9)), np.zeros((P, 3)), np.zeros(P), np.zeros((P, 9))
     counts = np.zeros((P, 4), dtype=np.int64)
     best, n_good, h_count, h_best, info = (np.zeros(P, dtype=np.int32) for _ in range(5))
@@ -1521,16 +1506,7 @@ def _register(name, k, min_n, slots, K, X, view_start, pt_idx, xy, samples, thre
     threshold = float(threshold)
     bad = (not (np.isfinite(threshold) and threshold > 0) or int(min_inliers) < min_n or int(refit_rounds) < 0
            or int(max_nfev) <= 0 or H > 1 << 20 or not _csr_ok(vs, pt, len(X)))
-    if not bad:
-        n_v = np.diff(vs)
-        live = n_v >= min_n
-        if live.any():
-            s = samples[live]
-            srt = np.sort(s, axis=2)
-            bad = bool((s.min(axis=(1, 2)) < 0).any() or (s.max(axis=(1, 2)) >= n_v[live]).any()
-                       or (srt[:, :, 1:] == srt[:, :, :-1]).any())
-            if not bad:
-                require_device()
+    _rows_rejected(bad, vs, len(pt), samples, min_n)
     multi = slots > 1
     per = (H, slots) if multi else (H,)
     C, R, cost = np.zeros((V, 3)), np.zeros((V, 9)), np.zeros(V)

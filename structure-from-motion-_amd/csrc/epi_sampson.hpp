@@ -194,4 +194,51 @@ __device__ __forceinline__ void epi_mask(const EpiPair &w, const double *F, doub
     cost = acc[1];
 }
 
+enum EpiStop { EPI_ROUNDS, EPI_UNCHANGED, EPI_WORSE, EPI_DECLINED };  // how epi_refit_rounds ended
+
+// The refit rounds of a pair's winner, from the state (F, n_inl, cost, mask) that
+// epi_mask left.  A round: propose(mask, n_inl, Fn) fits a model to the current
+// inliers, or returns false, which ends the rounds; Fn is scored into trial
+// and replaces the state only if it is not worse -- then accept() lets the
+// caller keep what else it holds of the proposal -- and an unchanged mask ends
+// the rounds.  mask: the pair's part of the output mask; trial: as many bytes
+// of scratch.
+template <int NT, int NV, class Propose, class Accept>
+__device__ __forceinline__ EpiStop epi_refit_rounds(const EpiPair &w, double thr2, double (&F)[9], int &n_inl,
+                                                    double &cost, uint8_t *mask, uint8_t *trial, int rounds,
+                                                    double (*red)[NV], Propose propose, Accept accept) {
+    for (int round = 0; round < rounds; ++round) {
+        double Fn[9], cost2;
+        int n2;
+        if (!propose(mask, n_inl, Fn)) return EPI_DECLINED;
+        epi_mask<NT>(w, Fn, thr2, trial, n2, cost2, red);
+        if (!not_worse(n2, cost2, n_inl, cost)) return EPI_WORSE;
+        const int changed = adopt_trial<NT>(mask, trial, w.n);
+#pragma unroll
+        for (int j = 0; j < 9; ++j) F[j] = Fn[j];
+        n_inl = n2;
+        cost = cost2;
+        accept();
+        if (!changed) return EPI_UNCHANGED;
+    }
+    return EPI_ROUNDS;
+}
+
+// The end of a refit kernel for pair p: without a winner (hyp < 0) the mask is
+// cleared; thread 0 stores the pair's scalars.
+template <int NT>
+__device__ __forceinline__ void epi_store_pair(int64_t p, int n, uint8_t *mask, int32_t hyp, int32_t count,
+                                               double cost, int n_inl, int info, double *cost_out, int32_t *n_inl_out,
+                                               int32_t *hyp_out, int32_t *count_out, int32_t *info_out) {
+    if (hyp < 0)
+        for (int i = threadIdx.x; i < n; i += NT) mask[i] = 0;
+    if (threadIdx.x == 0) {
+        cost_out[p] = cost;
+        n_inl_out[p] = n_inl;
+        hyp_out[p] = hyp;
+        count_out[p] = hyp < 0 ? 0 : count;
+        info_out[p] = info;
+    }
+}
+
 }  // namespace sfm

@@ -10,6 +10,8 @@
 //
 // The grid, the block table and the fixed-order sums are the scaffold's
 // (hyp_batch.hpp); k_ep_fit_score keeps the scaffold's device loops written out.
+// The refit's round loop (epi_sampson.hpp) and the host side of a call
+// (pair_verify.hpp) are shared with verify_pairs.hip.
 //
 //   k_ep_fit_score  Fit: one thread per hypothesis, four lanes of every wave at
 //                   a time, the 10 x 20 constraint matrix in LDS
@@ -31,7 +33,7 @@
 #include <cstring>
 
 #include "five_point.hpp"
-#include "hyp_batch.hpp"
+#include "pair_verify.hpp"
 
 #pragma clang fp contract(off)
 
@@ -216,9 +218,7 @@ k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
     double E[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double cost = 0.0;
     int info = -2, n_inl = 0;
-    if (bc < 0) {
-        for (int i = tid; i < n; i += EP_RT) mask[i] = 0;
-    } else {
+    if (bc >= 0) {
 #pragma unroll
         for (int j = 0; j < 9; ++j) E[j] = h_E[(p * H + bh) * 9 + j];
         ep_F(K, E, F);
@@ -246,41 +246,37 @@ k_ep_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
                 for (int j = 0; j < 5; ++j) g[j] = s[15 + j];
                 c = s[21] > 0.0 ? INFINITY : s[20];
             };
-            for (int round = 0; round < refit_rounds; ++round) {
-                double R[9], t[3];
-                if (!ep_factor(E, R, t)) {
-                    info = -4;
-                    break;
-                }
-                info = ep_lm(eval, R, t, max_nfev);
-                if (info < 0) break;
-                double G[9], En[9], Fn[9], cost2;
-                int n2;
-                ep_cross_mat(t, R, G);
-                vp_unit(G, En);
-                ep_F(K, En, Fn);
-                epi_mask<EP_RT>(w, Fn, thr2, trial, n2, cost2, red2);
-                if (!not_worse(n2, cost2, n_inl, cost)) break;
-                const int changed = adopt_trial<EP_RT>(mask, trial, n);
+            // a round: E = [t]x R from Levenberg-Marquardt on the factors of the current E; info is its
+            // last code, or -4 where E does not factor
+            double En[9];
+            epi_refit_rounds<EP_RT>(
+                w, thr2, F, n_inl, cost, mask, trial, refit_rounds, red2,
+                [&](const uint8_t *, int, double (&Fn)[9]) {
+                    double R[9], t[3], G[9];
+                    if (!ep_factor(E, R, t)) {
+                        info = -4;
+                        return false;
+                    }
+                    info = ep_lm(eval, R, t, max_nfev);
+                    if (info < 0) return false;
+                    ep_cross_mat(t, R, G);
+                    vp_unit(G, En);
+                    ep_F(K, En, Fn);
+                    return true;
+                },
+                [&] {
 #pragma unroll
-                for (int j = 0; j < 9; ++j) { E[j] = En[j]; F[j] = Fn[j]; }
-                n_inl = n2;
-                cost = cost2;
-                if (!changed) break;
-            }
+                    for (int j = 0; j < 9; ++j) E[j] = En[j];
+                });
         }
     }
-    if (tid == 0) {
+    if (tid == 0)
         for (int j = 0; j < 9; ++j) {
             E_out[9 * p + j] = E[j];
             F_out[9 * p + j] = F[j];
         }
-        cost_out[p] = cost;
-        n_inl_out[p] = n_inl;
-        hyp_out[p] = bc < 0 ? -1 : bh;
-        count_out[p] = bc < 0 ? 0 : bc;
-        info_out[p] = info;
-    }
+    epi_store_pair<EP_RT>(p, n, mask, bc < 0 ? -1 : bh, bc, cost, n_inl, info, cost_out, n_inl_out, hyp_out, count_out,
+                          info_out);
 }
 
 }  // namespace sfm
@@ -293,103 +289,37 @@ extern "C" int sfm_essential_pairs(const double *K, const int64_t *pair_start, i
                                    double *E, double *F, double *cost, int32_t *n_inliers, int32_t *best_hyp,
                                    int32_t *best_count, int32_t *info, uint8_t *inlier, int32_t *n_sol,
                                    int32_t *counts, double *models, int device) {
-    SFM_CHECK_ARG(P >= 0 && n_corr >= 0, "P < 0 or n_corr < 0");
-    SFM_CHECK_ARG(H >= 1 && H <= (int64_t)1 << 20, "H must lie in [1, 2^20]");
-    SFM_CHECK_ARG(std::isfinite(threshold) && threshold > 0.0, "threshold must be finite and positive");
-    SFM_CHECK_ARG(min_inliers >= 5, "min_inliers must be at least 5");
-    SFM_CHECK_ARG(refit_rounds >= 0, "refit_rounds < 0");
-    SFM_CHECK_ARG(max_nfev > 0, "max_nfev must be positive");
-    SFM_CHECK_ARG(P < (int64_t)0x7fffffff / (H * EP_MAX_SOL), "P x H too large for one call");
-    SFM_CHECK_ARG(K && pair_start, "null pointer");
-    for (int j = 0; j < 9; ++j) SFM_CHECK_ARG(std::isfinite(K[j]), "K is not finite");
-    EpK Ki;
-    const double det = inv3_adjugate(K, Ki.ki);
-    SFM_CHECK_ARG(std::isfinite(det) && det != 0.0, "K is singular");
-    for (int j = 0; j < 9; ++j) SFM_CHECK_ARG(std::isfinite(Ki.ki[j]), "K has no finite inverse");
-    SFM_TRY(check_csr(pair_start, P, n_corr, "pair_start", "correspondence", 0x7fffffff,
-                      "a pair has too many correspondences"));
-    const int64_t n_live = count_live(pair_start, P, 5);
-    SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
-    SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    SFM_TRY(check_samples(pair_start, P, samples, H, 5, 5, "sample outside [0, n_p)"));
-    if (P == 0) return 0;
-    SFM_CHECK_ARG(E && F && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
-                  "null pointer");
-    // info -1: fewer than five correspondences
-    for (int64_t p = 0; p < P; ++p) {
-        if (pair_start[p + 1] - pair_start[p] >= 5) continue;
-        for (int j = 0; j < 9; ++j) {
-            E[9 * p + j] = 0.0;
-            F[9 * p + j] = 0.0;
-        }
-        cost[p] = 0.0;
-        n_inliers[p] = 0;
-        best_hyp[p] = -1;
-        best_count[p] = 0;
-        info[p] = -1;
-        for (int64_t k = pair_start[p]; k < pair_start[p + 1]; ++k) inlier[k] = 0;
-        if (n_sol) std::memset(n_sol + p * H, 0, (size_t)H * sizeof(int32_t));
-        if (counts) std::memset(counts + p * H * EP_MAX_SOL, 0, (size_t)H * EP_MAX_SOL * sizeof(int32_t));
-        if (models) std::memset(models + p * H * EP_MAX_SOL * 9, 0, (size_t)H * EP_MAX_SOL * 9 * sizeof(double));
-    }
-    if (n_live == 0) return 0;
-
-    ThreadCtx *c = thread_ctx(device);
-    if (!c) return SFM_ERR_HIP;
-    TileTable tt;
-    SFM_TRY(tt.build(c->pinned, n_live, pair_start, P, 5, H, EP_HT, EP_TILE));
-
-    const size_t PH = (size_t)P * (size_t)H;
-    Pack in(c->buf[0]), out(c->buf[1]);
-    const auto i_ps = in.add<int64_t>(P + 1);
-    const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
-    const auto i_s = in.add<int32_t>(5 * PH);
-    const auto i_t = in.add<int32_t>(tt.words());  // the block table
-    const auto o_E = out.add<double>(9 * P), o_F = out.add<double>(9 * P), o_cost = out.add<double>(P);
-    const auto o_info = out.add<int32_t>(P), o_ninl = out.add<int32_t>(P);
-    const auto o_hyp = out.add<int32_t>(P), o_bc = out.add<int32_t>(P);
-    const auto o_ns = out.add<int32_t>(PH), o_hc = out.add<int32_t>(PH);
-    const auto o_hs = out.add<double>(PH), o_hE = out.add<double>(9 * PH);
-    // the per-solution tables exist on the device only when they are asked for
-    const auto o_cnt = out.add<int32_t>(counts ? EP_MAX_SOL * PH : 0);
-    const auto o_m = out.add<double>(models ? 9 * EP_MAX_SOL * PH : 0);
-    const auto o_mask = out.add<uint8_t>(n_corr), o_m2 = out.add<uint8_t>(n_corr);  // o_m2: the refits' trial mask
-    SFM_TRY(in.reserve());
-    SFM_TRY(out.reserve());
-    hipStream_t s = c->stream;
-    CallTimer tm(c);
-    SFM_TRY(tm.mark(s));
-    SFM_TRY(in.upload(i_ps, pair_start, s));
-    SFM_TRY(in.upload(i_x1, x1, s));
-    SFM_TRY(in.upload(i_x2, x2, s));
-    SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, tt.blk, s));
-    SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_ep_fit_score, dim3((unsigned)tt.blocks), dim3(EP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
-                       in.ptr(i_x2), in.ptr(i_s), (int32_t)H, in.ptr(i_t), in.ptr(i_t, n_live + 1), (int32_t)n_live,
-                       Ki, threshold, out.ptr(o_ns), out.ptr(o_hc), out.ptr(o_hs), out.ptr(o_hE),
-                       counts ? out.ptr(o_cnt) : nullptr, models ? out.ptr(o_m) : nullptr);
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(tm.split(s));  // [3]: the fit-and-score kernel alone
-    hipLaunchKernelGGL(k_ep_refit, dim3((unsigned)P), dim3(EP_RT), 0, s, in.ptr(i_ps), in.ptr(i_x1), in.ptr(i_x2),
-                       (int32_t)H, Ki, threshold, min_inliers, refit_rounds, max_nfev, out.ptr(o_hc), out.ptr(o_hs),
-                       out.ptr(o_hE), out.ptr(o_m2), out.ptr(o_E), out.ptr(o_F), out.ptr(o_cost), out.ptr(o_ninl),
-                       out.ptr(o_hyp), out.ptr(o_bc), out.ptr(o_info), out.ptr(o_mask));
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(tm.mark(s));
-    const size_t S = (size_t)H * EP_MAX_SOL;
-    SFM_TRY(for_each_live_run(pair_start, P, 5, [&](int64_t p0, int64_t p1, int64_t k0, int64_t k1) -> int {
-        SFM_TRY(out.download_rows(E, o_E, 9, p0, p1, s));
-        SFM_TRY(out.download_rows(F, o_F, 9, p0, p1, s));
-        SFM_TRY(out.download_rows(cost, o_cost, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(info, o_info, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(best_count, o_bc, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
-        SFM_TRY(out.download_rows(n_sol, o_ns, H, p0, p1, s));
-        SFM_TRY(out.download_rows(counts, o_cnt, S, p0, p1, s));
-        return out.download_rows(models, o_m, 9 * S, p0, p1, s);
-    }));
-    return tm.finish(s);
+    static const PairSpec spec{5, 5, EP_MAX_SOL, EP_HT, EP_TILE, true, "min_inliers must be at least 5"};
+    Slot<int32_t> o_ns, o_hc, o_cnt;
+    Slot<double> o_hs, o_hE, o_m;
+    EpK Ki{};
+    if (K) (void)inv3_adjugate(K, Ki.ki);  // pair_run checks K and this inverse before a kernel reads it
+    return pair_run(
+        spec, K, pair_start, P, x1, x2, n_corr, samples, H, threshold, min_inliers, refit_rounds, max_nfev, E, F, cost,
+        n_inliers, best_hyp, best_count, info, inlier, n_sol, counts, models, device,
+        [&](Pack &out, size_t PH) {
+            o_ns = out.add<int32_t>(PH), o_hc = out.add<int32_t>(PH);
+            o_hs = out.add<double>(PH), o_hE = out.add<double>(9 * PH);
+            // the per-solution tables exist on the device only when they are asked for
+            o_cnt = out.add<int32_t>(counts ? EP_MAX_SOL * PH : 0);
+            o_m = out.add<double>(models ? 9 * EP_MAX_SOL * PH : 0);
+        },
+        [&](const PairCall &c, int refit) {
+            if (!refit)
+                hipLaunchKernelGGL(k_ep_fit_score, dim3((unsigned)c.blocks), dim3(EP_THREADS), 0, c.s, c.ps, c.x1, c.x2,
+                                   c.samples, (int32_t)c.H, c.blk_start, c.tab, (int32_t)c.n_live, Ki, c.threshold,
+                                   c.out.ptr(o_ns), c.out.ptr(o_hc), c.out.ptr(o_hs), c.out.ptr(o_hE),
+                                   counts ? c.out.ptr(o_cnt) : nullptr, models ? c.out.ptr(o_m) : nullptr);
+            else
+                hipLaunchKernelGGL(k_ep_refit, dim3((unsigned)c.P), dim3(EP_RT), 0, c.s, c.ps, c.x1, c.x2, (int32_t)c.H,
+                                   Ki, c.threshold, c.min_inliers, c.refit_rounds, c.max_nfev, c.out.ptr(o_hc),
+                                   c.out.ptr(o_hs), c.out.ptr(o_hE), c.mask2, c.E, c.F, c.cost, c.n_inl, c.hyp, c.count,
+                                   c.info, c.mask);
+        },
+        [&](const PairCall &c, int64_t p0, int64_t p1) -> int {
+            const size_t S = (size_t)c.H * EP_MAX_SOL;
+            SFM_TRY(c.out.download_rows(n_sol, o_ns, c.H, p0, p1, c.s));
+            SFM_TRY(c.out.download_rows(counts, o_cnt, S, p0, p1, c.s));
+            return c.out.download_rows(models, o_m, 9 * S, p0, p1, c.s);
+        });
 }

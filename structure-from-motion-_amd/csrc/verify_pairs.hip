@@ -10,7 +10,8 @@
 // the Sampson distance (epi_sampson.hpp).  Differs on purpose.
 //
 // The grid, the block table, the tile loop and the fixed-order sums are the
-// scaffold's (hyp_batch.hpp).
+// scaffold's (hyp_batch.hpp), the refit's round loop epi_sampson.hpp's and the
+// host side of a call pair_verify.hpp's, both shared with essential_pairs.hip.
 //
 //   k_vp_fit_score  Fit: a hypothesis belongs to 8 lanes, one design row each
 //                   (vp_fit_group8).  Score: a wave per hypothesis, the inlier
@@ -29,7 +30,7 @@
 
 #include "dlt_general.hpp"
 #include "epi_sampson.hpp"
-#include "hyp_batch.hpp"
+#include "pair_verify.hpp"
 #include "select.hpp"
 
 #pragma clang fp contract(off)
@@ -305,43 +306,29 @@ k_vp_refit(const int64_t *__restrict__ pair_start, const double2 *__restrict__ x
     }
     double F[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, cost = 0.0;
     int info = -2, n_inl = 0;
-    if (bh < 0) {
-        for (int i = tid; i < n; i += VP_RT) mask[i] = 0;
-    } else {
+    if (bh >= 0) {
         const double *m = models + (p * H + bh) * 9;
 #pragma unroll
         for (int j = 0; j < 9; ++j) F[j] = m[j];
         epi_mask<VP_RT>(w, F, thr2, mask, n_inl, cost, red);
         info = -3;
         if (bc >= min_inliers) {
-            info = refit_rounds > 0 ? 2 : 0;
-            for (int round = 0; round < refit_rounds; ++round) {
-                if (n_inl < 8) break;
-                double Fn[9], cost2;
-                int n2;
-                vp_refit(w, mask, n_inl, red, Rs, sFn, Fn);
-                epi_mask<VP_RT>(w, Fn, thr2, trial, n2, cost2, red);
-                if (!not_worse(n2, cost2, n_inl, cost)) break;
-                const int changed = adopt_trial<VP_RT>(mask, trial, n);
-#pragma unroll
-                for (int j = 0; j < 9; ++j) F[j] = Fn[j];
-                n_inl = n2;
-                cost = cost2;
-                if (!changed) {
-                    info = 1;
-                    break;
-                }
-            }
+            // a round: the least-squares fit over the inliers, while there are eight of them
+            const EpiStop stop = epi_refit_rounds<VP_RT>(
+                w, thr2, F, n_inl, cost, mask, trial, refit_rounds, red,
+                [&](const uint8_t *cur, int n_cur, double (&Fn)[9]) {
+                    if (n_cur < 8) return false;
+                    vp_refit(w, cur, n_cur, red, Rs, sFn, Fn);
+                    return true;
+                },
+                [] {});
+            info = stop == EPI_UNCHANGED ? 1 : refit_rounds > 0 ? 2 : 0;
         }
     }
-    if (tid == 0) {
+    if (tid == 0)
         for (int j = 0; j < 9; ++j) F_out[9 * p + j] = F[j];
-        cost_out[p] = cost;
-        n_inl_out[p] = n_inl;
-        hyp_out[p] = (int32_t)bh;
-        count_out[p] = bh < 0 ? 0 : bc;
-        info_out[p] = info;
-    }
+    epi_store_pair<VP_RT>(p, n, mask, (int32_t)bh, bc, cost, n_inl, info, cost_out, n_inl_out, hyp_out, count_out,
+                          info_out);
 }
 
 }  // namespace sfm
@@ -353,85 +340,25 @@ extern "C" int sfm_verify_pairs(const int64_t *pair_start, int64_t P, const doub
                                 int32_t min_inliers, int32_t refit_rounds, double *F, double *cost,
                                 int32_t *n_inliers, int32_t *best_hyp, int32_t *best_count, int32_t *info,
                                 uint8_t *inlier, int32_t *counts, double *models, int device) {
-    SFM_CHECK_ARG(P >= 0 && n_corr >= 0, "P < 0 or n_corr < 0");
-    SFM_CHECK_ARG(H >= 1 && H <= (int64_t)1 << 20, "H must lie in [1, 2^20]");
-    SFM_CHECK_ARG(std::isfinite(threshold) && threshold > 0.0, "threshold must be finite and positive");
-    SFM_CHECK_ARG(min_inliers >= 8, "min_inliers must be at least 8");
-    SFM_CHECK_ARG(refit_rounds >= 0, "refit_rounds < 0");
-    SFM_CHECK_ARG(P < (int64_t)0x7fffffff / H, "P x H too large for one call");
-    SFM_CHECK_ARG(pair_start, "null pointer");
-    SFM_TRY(check_csr(pair_start, P, n_corr, "pair_start", "correspondence", 0x7fffffff,
-                      "a pair has too many correspondences"));
-    const int64_t n_live = count_live(pair_start, P, 8);
-    SFM_CHECK_ARG(n_corr == 0 || (x1 && x2), "null pointer");
-    SFM_CHECK_ARG(n_live == 0 || samples, "null pointer");
-    SFM_TRY(check_samples(pair_start, P, samples, H, 8, 8, "sample outside [0, n_p)"));
-    if (P == 0) return 0;
-    SFM_CHECK_ARG(F && cost && n_inliers && best_hyp && best_count && info && (inlier || n_corr == 0),
-                  "null pointer");
-    // info -1: fewer than eight correspondences
-    for (int64_t p = 0; p < P; ++p) {
-        if (pair_start[p + 1] - pair_start[p] >= 8) continue;
-        for (int j = 0; j < 9; ++j) F[9 * p + j] = 0.0;
-        cost[p] = 0.0;
-        n_inliers[p] = 0;
-        best_hyp[p] = -1;
-        best_count[p] = 0;
-        info[p] = -1;
-        for (int64_t k = pair_start[p]; k < pair_start[p + 1]; ++k) inlier[k] = 0;
-        if (counts) std::memset(counts + p * H, 0, (size_t)H * sizeof(int32_t));
-        if (models) std::memset(models + p * H * 9, 0, (size_t)H * 9 * sizeof(double));
-    }
-    if (n_live == 0) return 0;
-
-    ThreadCtx *c = thread_ctx(device);
-    if (!c) return SFM_ERR_HIP;
-    TileTable tt;
-    SFM_TRY(tt.build(c->pinned, n_live, pair_start, P, 8, H, VP_HT, VP_TILE));
-
-    const size_t PH = (size_t)P * (size_t)H;
-    Pack in(c->buf[0]), out(c->buf[1]);
-    const auto i_ps = in.add<int64_t>(P + 1);
-    const auto i_x1 = in.add<double2>(n_corr), i_x2 = in.add<double2>(n_corr);
-    const auto i_s = in.add<int32_t>(8 * PH);
-    const auto i_t = in.add<int32_t>(tt.words());  // the block table
-    const auto o_F = out.add<double>(9 * P), o_cost = out.add<double>(P);
-    const auto o_info = out.add<int32_t>(P), o_ninl = out.add<int32_t>(P);
-    const auto o_hyp = out.add<int32_t>(P), o_bc = out.add<int32_t>(P), o_cnt = out.add<int32_t>(PH);
-    const auto o_m = out.add<double>(9 * PH);
-    const auto o_mask = out.add<uint8_t>(n_corr), o_m2 = out.add<uint8_t>(n_corr);  // o_m2: the refits' trial mask
-    SFM_TRY(in.reserve());
-    SFM_TRY(out.reserve());
-    hipStream_t s = c->stream;
-    CallTimer tm(c);
-    SFM_TRY(tm.mark(s));
-    SFM_TRY(in.upload(i_ps, pair_start, s));
-    SFM_TRY(in.upload(i_x1, x1, s));
-    SFM_TRY(in.upload(i_x2, x2, s));
-    SFM_TRY(in.upload(i_s, samples, s));
-    SFM_TRY(in.upload(i_t, tt.blk, s));
-    SFM_TRY(tm.mark(s));
-    hipLaunchKernelGGL(k_vp_fit_score, dim3((unsigned)tt.blocks), dim3(VP_THREADS), 0, s, in.ptr(i_ps), in.ptr(i_x1),
-                       in.ptr(i_x2), in.ptr(i_s), (int32_t)H, in.ptr(i_t), in.ptr(i_t, n_live + 1), (int32_t)n_live,
-                       threshold, out.ptr(o_m), out.ptr(o_cnt));
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(tm.split(s));  // [3]: the fit-and-score kernel alone
-    hipLaunchKernelGGL(k_vp_refit, dim3((unsigned)P), dim3(VP_RT), 0, s, in.ptr(i_ps), in.ptr(i_x1), in.ptr(i_x2),
-                       (int32_t)H, threshold, min_inliers, refit_rounds, out.ptr(o_m), out.ptr(o_cnt), out.ptr(o_m2),
-                       out.ptr(o_F), out.ptr(o_cost), out.ptr(o_ninl), out.ptr(o_hyp), out.ptr(o_bc),
-                       out.ptr(o_info), out.ptr(o_mask));
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(tm.mark(s));
-    SFM_TRY(for_each_live_run(pair_start, P, 8, [&](int64_t p0, int64_t p1, int64_t k0, int64_t k1) -> int {
-        SFM_TRY(out.download_rows(F, o_F, 9, p0, p1, s));
-        SFM_TRY(out.download_rows(cost, o_cost, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(info, o_info, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(n_inliers, o_ninl, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(best_hyp, o_hyp, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(best_count, o_bc, 1, p0, p1, s));
-        SFM_TRY(out.download_rows(inlier, o_mask, 1, k0, k1, s));
-        SFM_TRY(out.download_rows(counts, o_cnt, H, p0, p1, s));
-        return out.download_rows(models, o_m, 9 * H, p0, p1, s);
-    }));
-    return tm.finish(s);
+    static const PairSpec spec{8, 8, 1, VP_HT, VP_TILE, false, "min_inliers must be at least 8"};
+    Slot<int32_t> o_cnt;
+    Slot<double> o_m;
+    return pair_run(
+        spec, nullptr, pair_start, P, x1, x2, n_corr, samples, H, threshold, min_inliers, refit_rounds, 0, nullptr, F,
+        cost, n_inliers, best_hyp, best_count, info, inlier, nullptr, counts, models, device,
+        [&](Pack &out, size_t PH) { o_cnt = out.add<int32_t>(PH), o_m = out.add<double>(9 * PH); },
+        [&](const PairCall &c, int refit) {
+            if (!refit)
+                hipLaunchKernelGGL(k_vp_fit_score, dim3((unsigned)c.blocks), dim3(VP_THREADS), 0, c.s, c.ps, c.x1, c.x2,
+                                   c.samples, (int32_t)c.H, c.blk_start, c.tab, (int32_t)c.n_live, c.threshold,
+                                   c.out.ptr(o_m), c.out.ptr(o_cnt));
+            else
+                hipLaunchKernelGGL(k_vp_refit, dim3((unsigned)c.P), dim3(VP_RT), 0, c.s, c.ps, c.x1, c.x2, (int32_t)c.H,
+                                   c.threshold, c.min_inliers, c.refit_rounds, c.out.ptr(o_m), c.out.ptr(o_cnt),
+                                   c.mask2, c.F, c.cost, c.n_inl, c.hyp, c.count, c.info, c.mask);
+        },
+        [&](const PairCall &c, int64_t p0, int64_t p1) -> int {
+            SFM_TRY(c.out.download_rows(counts, o_cnt, c.H, p0, p1, c.s));
+            return c.out.download_rows(models, o_m, 9 * c.H, p0, p1, c.s);
+        });
 }

@@ -240,3 +240,9 @@ def test_store_round_trip():
     for ij in ((0, 2), (1, 2)):
         for k in range(2):
             assert err["calibrated", ij][k] <= FACTOR * err["uncalibrated", ij][k], (ij, k)
+
+
+def test_every_output_keeps_the_bits_recorded_before_the_shared_driver():
+    import _sfmcore as core
+    import test_verify_pairs_gpu as vpg
+    vpg.check_stages_keep_their_bits(core, "E")

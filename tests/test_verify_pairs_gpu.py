@@ -277,3 +277,54 @@ def test_p3data_counts_are_numpys(core):
         assert n_inl[p] >= count[p] and inl[s:e].sum() == n_inl[p]
         print(f"P3Data pair {tuple(pair_ij[p] + 1)}: {n_inl[p]} inliers of {e - s} matches "
               f"(best hypothesis {count[p]}, info {info[p]})")
+
+
+# ------------------------------------------------- the batch recorded before the stages shared a driver
+# tests/golden/pair_stages_parent.npz (make_golden_pair_stages.py): every output of sfm_verify_pairs ("F") and
+# sfm_essential_pairs ("E") on one batch, as the commit before pair_verify.hpp returned them.
+STAGE_SIZES = (0, 8, 5, 9, 40, 4, 1025, 120, 300, 7)   # dead pairs first, in the middle and last
+STAGE_H = 65
+STAGE_CALLS = {"main": {}, "h1": {"H": 1}, "tight": {"threshold": 1e-9}, "none": {"threshold": 1e-170},
+               "high": {"min_inliers": 100000}, "rounds0": {"refit_rounds": 0}}
+STAGE_NAMES = {"F": ("F", "cost", "n_inliers", "inlier", "best_hyp", "best_count", "info", "counts", "models"),
+               "E": ("F", "cost", "n_inliers", "inlier", "best_hyp", "best_count", "info", "E", "n_sol", "counts",
+                     "models")}
+
+
+def stages_batch(seed):
+    """cfg2's two cameras: pairs of nine and more with 1 px noise and 30 % of their matches wrong"""
+    made = [vp.make_pair([seed, p], n, 1.0 if n >= 9 else 0.2, 0.3 if n >= 9 else 0.0)
+            for p, n in enumerate(STAGE_SIZES)]
+    ps = np.concatenate([[0], np.cumsum(STAGE_SIZES)]).astype(np.int64)
+    return ps, np.concatenate([m[0] for m in made]), np.concatenate([m[1] for m in made])
+
+
+def stages_run(core, stage, seed, calls=STAGE_CALLS):
+    """{"<stage>_<call>_<output>": array} over ``calls``"""
+    ps, x1, x2 = stages_batch(seed)
+    out = {}
+    for call, kw in calls.items():
+        kw = dict(kw)
+        H = kw.pop("H", STAGE_H)
+        if stage == "F":
+            got = core.verify_pairs(ps, x1, x2, core.pair_samples(np.diff(ps), H, seed), want_counts=True,
+                                    want_models=True, **kw)
+        else:
+            got = core.essential_pairs(vp.K, ps, x1, x2, core.essential_samples(np.diff(ps), H, seed),
+                                       want_counts=True, want_models=True, **kw)
+        out.update({f"{stage}_{call}_{name}": a for name, a in zip(STAGE_NAMES[stage], got)})
+    return out
+
+
+def check_stages_keep_their_bits(core, stage):
+    gold = np.load(os.path.join(GOLDEN, "pair_stages_parent.npz"))
+    got = stages_run(core, stage, int(gold["seed"]))
+    assert len(got) == len(STAGE_CALLS) * len(STAGE_NAMES[stage])
+    for key, a in got.items():
+        # an array equal to the main call's is stored once
+        ref = gold[key if key in gold.files else f"{stage}_main_" + key.split("_", 2)[2]]
+        assert a.dtype == ref.dtype and np.array_equal(a, ref), key
+
+
+def test_every_output_keeps_the_bits_recorded_before_the_shared_driver(core):
+    check_stages_keep_their_bits(core, "F")
