@@ -9,7 +9,7 @@
 // applied matrix-free from the adjacency, the normalisation by c and the new
 // edge weights and target lengths.  A node's entries are walked by a group of
 // G lanes (G a power of two <= 64 chosen on the host from the size of the
-// graph): lane g takes the entries g, g + G, .. in their order and the group's
+// graph, position_plan.hpp): lane g takes the entries g, g + G, .. in their order and the group's
 // partial sums meet in a shuffle tree, so a node of any degree is a loop, never
 // a lane per entry.  Every sum over nodes or edges (the two CG dot products,
 // |r|, |rhs|, the two sums of c) is a per-thread sum in index order, a shuffle
@@ -39,14 +39,13 @@
 #include <cmath>
 #include <cstring>
 
+#include "position_plan.hpp"
 #include "staging.hpp"
 #include "view_graph.hpp"
 
 namespace sfm {
 
-constexpr int PA_MAX_NODES = SFM_POSITIONS_PATH1_MAX_NODES;  // path 1: solved nodes, the root included
-constexpr int PA_T1 = 512;       // path 1's workgroup: at 1024 the kernel's 166 VGPRs would spill
-constexpr int PA_T2 = 256;       // path 2's workgroups
+static_assert(PA_MAX_NODES == SFM_POSITIONS_PATH1_MAX_NODES, "position_plan.hpp and sfmcore.h name one bound");
 constexpr int PA_CG_BATCH = 8;   // path 2: CG iterations launched between two looks at the stop word
 constexpr double PA_FLOOR = 1e-3;  // the least target length and the least |v| of a weight
 
@@ -512,16 +511,6 @@ __global__ __launch_bounds__(PA_T2) void k_pa_reweight(PaGraph gr, PaParams pr, 
     if (e < gr.n_edges) pa_reweight_edge(gr, pr, eo, (int32_t)e, b.x);
 }
 
-// lanes per node: the power of two next above an eighth of the mean entries per node, 1 .. 64; for path 1
-// no more than fills its one workgroup once
-static int pa_group_lanes(int64_t n_entries, int32_t n_nodes, bool one_workgroup) {
-    int G = 1;
-    while (G < 64 && (int64_t)G * 8 * n_nodes < n_entries) G *= 2;
-    if (one_workgroup)
-        while (G > 1 && (int64_t)G * n_nodes > PA_T1) G /= 2;
-    return G;
-}
-
 }  // namespace sfm
 
 using namespace sfm;
@@ -620,8 +609,9 @@ extern "C" int sfm_average_positions(int32_t n_images, const int32_t *pair_ij, c
     }
     const int32_t M = (int32_t)solved.size();
     const int64_t El = (int64_t)edges.size();
-    const int use_path = M == 0 ? 0 : path ? path : M <= PA_MAX_NODES ? 1 : 2;
-    SFM_CHECK_ARG(!(use_path == 1 && M > PA_MAX_NODES), "path 1 takes at most 512 solved nodes");
+    const PaPlan plan = pa_plan(M, El, path);  // position_plan.hpp
+    const int use_path = plan.path;
+    SFM_CHECK_ARG(plan.fits, "path 1 takes at most 512 solved nodes");
 
     // from here on the outputs are written
     for (int32_t n = 0; n < N; ++n) {
@@ -656,7 +646,7 @@ extern "C" int sfm_average_positions(int32_t n_images, const int32_t *pair_ij, c
     root = 0;
     for (int32_t n = 1; n < M; ++n)
         if (adj_start[(size_t)n + 1] - adj_start[n] > adj_start[(size_t)root + 1] - adj_start[root]) root = n;
-    const int G = pa_group_lanes(2 * El, M, use_path == 1);
+    const int G = plan.G;
 
     ThreadCtx *c = thread_ctx(device);
     if (!c) return SFM_ERR_HIP;
@@ -672,7 +662,7 @@ extern "C" int sfm_average_positions(int32_t n_images, const int32_t *pair_ij, c
     const auto o_ticks = out.add<long long>(1);
     const auto o_state = out.add<PaState>(1);
     const auto w_w = work.add<double>(El), w_s = work.add<double>(El);
-    const int32_t nb_group = ceil_div((int64_t)M * G, PA_T2), nb_node = ceil_div(M, PA_T2), nb_edge = ceil_div(El, PA_T2);
+    const int32_t nb_group = plan.nb_group, nb_node = plan.nb_node, nb_edge = plan.nb_edge;
     const size_t v3 = use_path == 2 ? 3 * (size_t)M : 0;
     const auto w_r = work.add<double>(v3), w_z = work.add<double>(v3), w_q = work.add<double>(v3);
     const auto w_p0 = work.add<double>(v3), w_p1 = work.add<double>(v3), w_D = work.add<double>(2 * v3);
@@ -684,7 +674,7 @@ extern "C" int sfm_average_positions(int32_t n_images, const int32_t *pair_ij, c
     SFM_TRY(out.reserve());
     SFM_TRY(work.reserve());
 
-    const size_t lds = (size_t)M * 168 + 3 * (PA_T1 / 64) * sizeof(double);
+    const size_t lds = plan.lds_bytes;
     if (use_path == 1)
         SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pa_persistent),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
