@@ -278,10 +278,15 @@ def pair_rotations(verified, init, min_points=30):
 def average_rotations(pair_ij, R_rel, n_images, weight=None, **args):
     """Every camera's rotation from the pairs' relative rotations in one device
     call (``_sfmcore.average_rotations``, which documents the algorithm, the
-    gauge and ``args``: seed, threshold, consensus_sweeps, max_sweeps, tol --
-    policy defaults to override, not measured quantities).
+    gauge and ``args``: seed, threshold, consensus_sweeps, max_sweeps, tol, and
+    refit -- "jacobi", the default, or "cg", the Gauss-Newton refit with the same
+    optimum, with rounds, cg_tol, cg_max_iters -- policy defaults to override,
+    not measured quantities).  Measured: "cg" reaches ``tol`` in 4 to 5 rounds
+    on graphs of up to 300 images; at 10,000 images the default 10 rounds end at
+    a step of 7.8e-8, so raise ``rounds`` there and read ``step``.
     Returns (order, out): ``out`` is ``_sfmcore.average_rotations``'s tuple (R,
-    edge_angle, edge_inlier, n_inlier_edges, group, info, level, sweeps);
+    edge_angle, edge_inlier, n_inlier_edges, group, info, level, sweeps, and
+    with refit="cg" cg_iters, cg_residual, step after them);
     ``order`` lists the images of the largest group first (the lowest label on
     ties), then the other groups by decreasing size, images ascending inside a
     group.  Rotations are consistent inside one group only: R[order[:k]] with k
